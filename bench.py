@@ -34,7 +34,7 @@ LOSS = "binary_crossentropy+1.0*dice_loss"
 LOSS_SOFTMAX = "categorical_crossentropy+1.0*dice_loss"
 # algorithmic work per trained image (BASELINE.md 3 / SURVEY 8d): conv MACs only, 2 FLOP/MAC, 3x forward
 FLOP_PER_IMAGE = 187.94e9
-PEAK_BF16_TFLOPS = 2500.0      # dense bf16 / fp16 MFMA, /opt/skills/guides/MI355X_MICROARCH.md chip table
+PEAK_BF16_TFLOPS = 2500.0      # dense bf16 / fp16 MFMA, the MI355X chip specification
 PEAK_HBM_GBS = 8000.0
 
 # BASELINE.json configs by index: network, input, batch per GPU, classes, the precision BASELINE.json names,
@@ -536,6 +536,33 @@ def dice_delta_vs_oracle(device):
     return out
 
 
+DUMP_LIMITS = {"logits": 30 << 18, "weights": 28 << 18, "bn_moving_stats": 4 << 18}   # elements (float32): 62 MiB over all files
+
+
+def _fixed_sample(a, limit):
+    """``a`` itself if it has at most ``limit`` elements, else the elements of its flattened form at ``limit`` sorted indices drawn
+    with numpy.random.RandomState(0): the same positions on every run of the same config."""
+    if a.size <= limit:
+        return a
+    idx = np.sort(np.random.RandomState(0).choice(a.size, limit, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(model, out_dir):
+    """--dump-outputs: what the last counted step handed to a caller of ``train_on_batch``, as <out_dir>/<name>.npy - its metrics
+    (metric_<name>.npy, float64 scalars), the logits of its forward pass (float32, the model's layout) and, after its Adam update, the
+    weights and the BatchNormalization moving statistics (float32, Keras layouts flattened and concatenated in name order).  An array
+    larger than its DUMP_LIMITS share is written as a fixed sample (_fixed_sample), so the files stay under 64 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in model.metrics().items():
+        np.save(os.path.join(out_dir, "metric_%s.npy" % k), np.float64(v))
+    np.save(os.path.join(out_dir, "logits.npy"), _fixed_sample(model.logits().astype(np.float32), DUMP_LIMITS["logits"]))
+    w = model.get_weights()
+    for name, keys in (("weights", sorted(model.plan.params)), ("bn_moving_stats", sorted(model.plan.states))):
+        flat = np.concatenate([np.asarray(w[k], np.float32).reshape(-1) for k in keys]) if keys else np.zeros(0, np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), _fixed_sample(flat, DUMP_LIMITS[name]))
+
+
 def main():
     # stdout carries exactly ONE line (the JSON): libraries that print to the C-level stdout (RCCL's version banner, MIOpen) are
     # moved to stderr for the lifetime of the process, the result is written to the original descriptor at the end
@@ -564,7 +591,12 @@ def main():
     ap.add_argument("--no-feed", action="store_true", help="skip the region fed from pinned host memory (profiler traces of the resident step only)")
     ap.add_argument("--sustain", type=float, default=8.0,
                     help="seconds of extra back-to-back steps after the counted ones, reported as `sustained` (0 = skip; 1-GPU runs only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the --steps counted steps (before any other region), write what the last of them computed to DIR/<name>.npy "
+                         "(rank 0): metrics, logits, updated weights and BatchNormalization statistics, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     cfg = dict(CONFIGS[args.config])
     if args.architecture and args.config != 1:
         raise SystemExit("--architecture applies to --config 1")
@@ -680,6 +712,8 @@ def main():
     for i in range(args.warmup):
         step(i)
     elapsed = timed(step, args.warmup, args.steps)          # the contract's region: raw uint8 batch RESIDENT in HBM
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)              # (the regions below train on: their steps are not the counted ones)
 
     # ---- the network alone (no augmentation launch): the part of the step the launch tables / floor tables describe.  Configs 3 / 4 only
     # (config 1 keeps its established region list); the batch in the plan's input buffers is the last augmented one

@@ -806,3 +806,46 @@ def test_folds_load_returns_the_first_items_of_the_fold():
     assert kf.cfg is cfg
     with pytest.raises(ValueError):
         pipeline.KFoldedDataSet(DS(), range(10)).augmentor(True)
+
+
+def test_bench_dump_outputs_stays_in_budget_and_samples_the_same_positions(tmp_path):
+    """bench.py --dump-outputs: one .npy per output in float32 / float64, under 64 MB in all however large the model, and an array over
+    its share sampled at the same positions on every call (two builds compare output for output)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Plan(object):
+        params = {"b/kernel": None, "a/kernel": None}
+        states = {"a_bn/moving_mean": None}
+
+    class Model(object):         # the accessors dump_outputs reads, at sizes over every share of the budget
+        plan = Plan()
+
+        def metrics(self):
+            return {"loss": 0.5, "dice": 0.25}
+
+        def logits(self):
+            return np.arange(9 << 20, dtype=np.float32).reshape(4, 1024, 1152, 2)
+
+        def get_weights(self):
+            return {"a/kernel": np.arange(5 << 20, dtype=np.float32).reshape(-1, 4), "b/kernel": -np.arange(4 << 20, dtype=np.float32),
+                    "a_bn/moving_mean": np.ones(3, np.float32)}
+
+    outs = []
+    for d in ("one", "two"):
+        bench.dump_outputs(Model(), str(tmp_path / d))
+        files = sorted(os.listdir(str(tmp_path / d)))
+        assert files == ["bn_moving_stats.npy", "logits.npy", "metric_dice.npy", "metric_loss.npy", "weights.npy"]
+        assert sum(os.path.getsize(str(tmp_path / d / f)) for f in files) <= 64 << 20
+        outs.append({f: np.load(str(tmp_path / d / f)) for f in files})
+    a, b = outs
+    assert a["metric_loss.npy"].dtype == np.float64 and float(a["metric_loss.npy"]) == 0.5
+    for f in ("logits.npy", "weights.npy", "bn_moving_stats.npy"):
+        assert a[f].dtype == np.float32 and np.array_equal(a[f], b[f])
+    assert np.array_equal(a["bn_moving_stats.npy"], np.ones(3, np.float32))
+    lg = a["logits.npy"]                                    # sampled: sorted distinct positions of the flattened logits
+    assert lg.shape == (bench.DUMP_LIMITS["logits"],) and np.all(np.diff(lg) > 0)
+    w = a["weights.npy"]                                    # name order: a/kernel (0 .. 5 Mi - 1) before b/kernel (0, -1, ...)
+    assert w.shape == (bench.DUMP_LIMITS["weights"],) and w[0] >= 0 and w[-1] <= 0
