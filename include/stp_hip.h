@@ -517,6 +517,21 @@ int stp_lovasz_hinge(const void* logits, const uint8_t* target, int32_t images, 
  * over the padded gradient tensor).  Same workspace and count as the loss call that wrote dlogits. */
 int stp_sigmoid_loss_bias_grad(const void* workspace, int64_t count, float* dbias, int32_t accumulate, void* stream);
 int stp_sigmoid(const void* logits, float* probs, int64_t count, int32_t dtype, void* stream);
+/* Multi-label sigmoid head (classes: C, activation: sigmoid, H x W x C {0,1} masks): C = 2..8 independent sigmoid channels of
+ * logits [pixels][ldc] (the first `classes` channels), target = one uint8 per pixel with bit c = class c.  weights5 (HOST pointer) as
+ * stp_sigmoid_loss_ex; every loss is the Keras / musket formula on the [pixels, classes] tensor: binary_crossentropy, binary_accuracy and
+ * focal_loss are means over pixels * classes elements, dice / iou ONE soft coefficient over the flattened tensor (smooth 1), jaccard_loss
+ * the per-pixel distance over the class axis (smooth 100) averaged over pixels.  scalars (fp32[12]) in the layout of stp_sigmoid_loss_ex;
+ * dlogits [pixels][dl_channels] gets the classes gradients x grad_scale and zero padding.  STP_E_BADARG for classes outside 2..8,
+ * ldc < classes or dl_channels < classes.  Workspace: stp_loss_workspace_bytes(). */
+int stp_sigmoid_multilabel_loss(const void* logits, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc,
+                                int32_t dtype, const float* weights5, float* scalars, void* dlogits, int32_t dl_channels,
+                                float grad_scale, void* workspace, size_t workspace_bytes, void* stream);
+/* Bias gradients of the multi-label class convolution: the gradient pass of stp_sigmoid_multilabel_loss leaves one partial sum per
+ * class and workgroup in its workspace; this adds them up in a fixed order into dbias[0 .. classes) (accumulate: +=).  Same workspace,
+ * pixels and classes as the loss call that wrote dlogits. */
+int stp_sigmoid_multilabel_bias_grad(const void* workspace, int64_t pixels, int32_t classes, float* dbias, int32_t accumulate,
+                                     void* stream);
 /* Multi-class head (activation: softmax, loss: categorical_crossentropy[+w*dice_loss]; schemas/segmentation.raml:12-21,
  * 62-63): channel softmax over the first `classes` (2..32) channels of logits [pixels][ldc], target = uint8 class index
  * per pixel.  scalars as stp_sigmoid_bce_dice with [1] = categorical_crossentropy and the sums taken over every

@@ -244,12 +244,16 @@ class PipelineConfig(generic.GenericTaskConfig):
     def predict_to_directory(self, spath, tpath, fold=0, stage=0, limit=-1, batchSize=32, binaryArray=False, ttflips=False):
         os.makedirs(tpath, exist_ok=True)
         from PIL import Image
+        multilabel = self.classes > 1 and self.all.get("activation") == "sigmoid"      # (independent sigmoid maps, H x W x classes)
         for items, probs in self.predict_on_directory(spath, fold=fold, stage=stage, limit=limit, batch_size=batchSize, ttflips=ttflips):
             for it, p in zip(items, probs):
                 scaled = self._scale_back(p, *it.x.shape[:2])
                 stem = it.id[0:it.id.index(".")] if "." in it.id else it.id
                 if binaryArray:
                     np.save(os.path.join(tpath, stem), scaled)
+                elif multilabel:              # one PNG per class: <stem>_<c>.png
+                    for c in range(scaled.shape[2]):
+                        Image.fromarray((scaled[:, :, c] * 255).astype(np.uint8)).save(os.path.join(tpath, "%s_%d.png" % (stem, c)))
                 else:
                     Image.fromarray((scaled[:, :, 0] * 255).astype(np.uint8)).save(os.path.join(tpath, stem + ".png"))
 

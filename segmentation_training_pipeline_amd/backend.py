@@ -22,17 +22,25 @@ CAPTURE_MODE = "thread_local"
 SCALAR_NAMES = ("loss", "binary_crossentropy", "dice_loss", "dice", "binary_accuracy")
 
 
-EXTENDED_LOSSES = ("iou_loss", "jaccard_loss", "focal_loss", "lovasz_loss")      # sigmoid head only (stp_sigmoid_loss_ex, stp_lovasz_hinge)
+EXTENDED_LOSSES = ("iou_loss", "jaccard_loss", "focal_loss", "lovasz_loss")      # sigmoid heads only (stp_sigmoid_loss_ex, stp_lovasz_hinge,
+                                                                                # stp_sigmoid_multilabel_loss: all but lovasz_loss)
+MAX_MULTILABEL_CLASSES = 8          # one target byte per pixel: bit c = class c
 
 
-def parse_loss(spec, classes=1, architecture=None):
+def is_multilabel(classes, activation):
+    """A head of C >= 2 independent sigmoid channels (``classes: C``, ``activation: sigmoid``: H x W x C {0,1} masks)."""
+    return int(classes) > 1 and activation == "sigmoid"
+
+
+def parse_loss(spec, classes=1, architecture=None, activation=None):
     """``"binary_crossentropy+0.1*dice_loss"`` -> (w_ce, w_dice) or, when the spec names one of the other registry entries
     of reference segmentation.py:15-22, (w_ce, w_dice, w_iou, w_jaccard, w_focal, w_lovasz)  (grammar: reference README.md:210-214).
-    The cross-entropy term is ``binary_crossentropy`` for the 1-class sigmoid head and ``categorical_crossentropy`` for
-    the softmax head (schemas/segmentation.raml:12-21)."""
-    ce = "binary_crossentropy" if classes == 1 else "categorical_crossentropy"
+    The cross-entropy term is ``binary_crossentropy`` for the sigmoid heads (one class, or ``activation="sigmoid"`` with several:
+    multi-label) and ``categorical_crossentropy`` for the softmax head (schemas/segmentation.raml:12-21)."""
+    sigmoid = classes == 1 or is_multilabel(classes, activation)
+    ce = "binary_crossentropy" if sigmoid else "categorical_crossentropy"
     w = {ce: 0.0, "dice_loss": 0.0}
-    if classes == 1 and architecture != "DeepLabV3":
+    if sigmoid and architecture != "DeepLabV3":
         w.update((k, 0.0) for k in EXTENDED_LOSSES)
     for term in str(spec).split("+"):
         term = term.strip()
@@ -44,6 +52,8 @@ def parse_loss(spec, classes=1, architecture=None):
         if name not in w:
             raise ValueError("loss %r is not available in the HIP backend (have: %s)" % (name, ", ".join(sorted(w))))
         w[name] += k
+    if classes > 1 and w.get("lovasz_loss"):
+        raise ValueError("lovasz_loss is not available for a multi-label head (the HIP backend has the binary Lovasz hinge of one class)")
     if any(w.get(k) for k in EXTENDED_LOSSES):
         return (w[ce], w["dice_loss"]) + tuple(w[k] for k in EXTENDED_LOSSES)
     return w[ce], w["dice_loss"]
@@ -59,8 +69,17 @@ class HipSegModel(object):
         if backbone not in nets.known_backbones() or (backbone in nets.VGG_BLOCKS and architecture not in ("Unet", "Linknet", "FPN", "PSPNet")) \
                 or ((backbone in ("mobilenetv2", "xception")) != (architecture == "DeepLabV3")):   # VGG: every segmentation_models architecture; MobileNetV2 / Xception: DeepLabV3 only
             raise ValueError("Unknown backbone")
-        if not ((classes == 1 and activation in ("sigmoid", None)) or (2 <= classes <= 32 and activation == "softmax")):
-            raise ValueError("the HIP backend trains 1-class sigmoid heads and 2..32-class softmax heads")
+        if is_multilabel(classes, activation):
+            if classes > MAX_MULTILABEL_CLASSES:
+                raise ValueError("the HIP backend trains multi-label sigmoid heads of 2..%d classes, not %d" % (MAX_MULTILABEL_CLASSES, classes))
+            if architecture == "DeepLabV3":
+                raise ValueError("the HIP DeepLabV3 has no multi-label sigmoid head (its loss runs on probabilities): use Unet, Linknet, FPN or PSPNet")
+        elif not ((classes == 1 and activation in ("sigmoid", None)) or (2 <= classes <= 32 and activation == "softmax")):
+            raise ValueError("the HIP backend trains 1-class sigmoid heads, 2..%d-class multi-label sigmoid heads and 2..32-class softmax heads"
+                             % MAX_MULTILABEL_CLASSES)
+        # the head's activation ("sigmoid" for one class or multi-label, "softmax"); (`activation(name)` reads a plan tensor)
+        self.head_activation = "softmax" if (classes > 1 and activation == "softmax") else "sigmoid"
+        self.multilabel = is_multilabel(classes, activation)
         self.architecture, self.backbone = architecture, backbone
         self.H, self.W, self.in_ch = int(input_shape[0]), int(input_shape[1]), int(input_shape[2])
         self.classes, self.batch, self.dtype = classes, int(batch), dtype
@@ -71,7 +90,7 @@ class HipSegModel(object):
         # architecture-specific graph options (FPN: pyramid_block_filters, segmentation_block_filters; PSPNet: downsample_factor,
         # psp_conv_filters - schemas/segmentation.raml:179-249), passed to the network definition as keywords
         self.net_kwargs = dict(net_kwargs or {})
-        self.loss_w = parse_loss(loss, classes, architecture)
+        self.loss_w = parse_loss(loss, classes, architecture, self.head_activation)
         self.optimizer = optimizer.lower()
         if self.optimizer not in ("adam", "sgd", "rmsprop", "nadam"):
             raise ValueError("optimizer %r is not available in the HIP backend (have: SGD, Adam, RMSprop, Nadam)" % optimizer)
@@ -152,10 +171,12 @@ class HipSegModel(object):
             kw = {"decoder_block_type": self.decoder_block_type} if self.architecture in ("Unet", "Linknet") else dict(self.net_kwargs)
             if self.architecture == "DeepLabV3" and self.backbone != "xception":
                 kw.pop("OS", None)                                   # (the output stride applies to the xception backbone only, model.py:296-297)
+            if self.multilabel:
+                kw["multilabel"] = True
             logits = nets.NETWORKS[self.architecture](plan, self.backbone, self.H, self.W, self.in_ch, self.classes,
                                                       self.decoder_filters, self.loss_w, with_loss=with_loss, **kw)
             if not with_loss and self.architecture != "DeepLabV3":      # (DeepLab's graph ends in probabilities itself)
-                (plan.sigmoid_out if self.classes == 1 else plan.softmax_out)(logits)
+                (plan.sigmoid_out if self.head_activation == "sigmoid" else plan.softmax_out)(logits)
             return logits
         return fn
 
@@ -438,7 +459,8 @@ class HipSegModel(object):
         return self._segments
 
     def load_batch(self, x, y=None):
-        """Copies a uint8 image batch [N,H,W,C] (and masks [N,H,W,1] in {0,1}) into the plan's input buffers."""
+        """Copies a uint8 image batch [N,H,W,C] (and masks [N,H,W,1] in {0,1}; a multi-label head also takes [N,H,W,classes] {0,1}
+        maps, packed here into class bits) into the plan's input buffers."""
         p = self.plan
         xi = p.inputs["image"].buf
         x = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
@@ -447,6 +469,9 @@ class HipSegModel(object):
         xi.copy_(x.reshape(xi.shape), non_blocking=True)
         if y is not None:
             yi = p.inputs["mask"].buf
+            if self.multilabel and y.shape[-1] == self.classes and y.ndim == 4:      # [N,H,W,C] {0,1} maps -> class bits per pixel
+                y = np.asarray(y.cpu() if isinstance(y, torch.Tensor) else y)
+                y = sum(((y[..., c] != 0).astype(np.uint8) << np.uint8(c)) for c in range(self.classes)).astype(np.uint8)
             y = torch.from_numpy(np.ascontiguousarray(y)) if isinstance(y, np.ndarray) else y
             yi.copy_(y.to(torch.uint8).reshape(yi.shape), non_blocking=True)
 
@@ -505,12 +530,13 @@ class HipSegModel(object):
     def metrics(self):
         s = self.plan.loss_scalars.cpu().numpy()
         out = dict(zip(SCALAR_NAMES, (float(v) for v in s[:5])))
-        if self.classes > 1:
+        if self.head_activation == "softmax":
             out["categorical_crossentropy"] = out.pop("binary_crossentropy")
         out["iou"], out["iot"] = float(s[8]), float(s[9])
         if len(self.loss_w) > 2:
             out["iou_loss"], out["jaccard_loss"], out["focal_loss"] = 1.0 - float(s[8]), float(s[10]), float(s[11])
-            out["lovasz_loss"] = float(s[12])
+            if not self.multilabel:
+                out["lovasz_loss"] = float(s[12])
         return out
 
     def logits(self):

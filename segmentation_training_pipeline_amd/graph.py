@@ -968,6 +968,9 @@ class Plan(object):
             if b is not None and b.trainable and out.meta.get("loss_bias_grad") and Cout == 1:
                 # the 1-class head: the loss gradient kernel left the per-workgroup sums of dL/dlogit in its workspace
                 self._emit(self.bwd, "stp_sigmoid_loss_bias_grad", self.ws_loss.data_ptr(), rows, self._gptr(b), 0)
+            elif b is not None and b.trainable and out.meta.get("loss_bias_grad") == "multilabel":
+                # the multi-label head: one partial sum per class and gradient workgroup, left by stp_sigmoid_multilabel_loss
+                self._emit(self.bwd, "stp_sigmoid_multilabel_bias_grad", self.ws_loss.data_ptr(), rows, Cout, self._gptr(b), 0)
             elif b is not None and b.trainable:
                 tmp = self._alloc((CoutB,), torch.float32)
                 self._emit(self.bwd, "stp_channel_sum", dy.data_ptr(), self.cdt, rows, CoutB, tmp.data_ptr(), 0,
@@ -1734,6 +1737,29 @@ class Plan(object):
                        self.ws_lovasz.data_ptr(), nbytes)
         logits.grad_ready = self.training
 
+    def sigmoid_multilabel_loss(self, logits, target, w_bce, w_dice, w_iou=0.0, w_jaccard=0.0, w_focal=0.0):
+        """Multi-label head (classes: C = 2..8, activation: sigmoid): C independent sigmoids and the weighted sum of
+        binary_crossentropy, dice_loss, iou_loss, jaccard_loss, focal_loss over the [pixels, C] tensor; target = one byte per
+        pixel, bit c = class c.  Seeds the backward pass."""
+        if not 2 <= logits.C <= 8:
+            raise StpShapeError("multi-label loss expects 2..8 classes")
+        if self.dry:
+            return
+        import ctypes
+        self.loss_scalars = self._alloc((16,), torch.float32)
+        self.loss_scalars.zero_()
+        dl = self._gradbuf(logits) if self.training else None
+        self._loss_weights = (ctypes.c_float * 5)(w_bce, w_dice, w_iou, w_jaccard, w_focal)     # host array read at launch
+        self._emit(self.fwd, "stp_sigmoid_multilabel_loss", logits.buf.data_ptr(), target.buf.data_ptr(), logits.rows, logits.C, logits.C,
+                   self.cdt, ctypes.addressof(self._loss_weights), self.loss_scalars.data_ptr(), dl.data_ptr() if dl is not None else None,
+                   logits.gradC, float(self.loss_scale), self.ws_loss.data_ptr(), self.ws_loss.numel() * 4)
+        if self.training and self.dls is not None:
+            self._emit(self.fwd, "stp_scale_by_device", dl.data_ptr(), logits.rows * logits.gradC, self.cdt, self.dls.data_ptr(), self.dls.data_ptr() + 16)
+        # the class convolution reads its C bias gradients from the gradient pass's per-workgroup, per-class sums (not when
+        # stp_scale_by_device rescales the gradient afterwards)
+        logits.meta["loss_bias_grad"] = "multilabel" if (self.training and self.dls is None) else False
+        logits.grad_ready = self.training
+
     def softmax_loss(self, logits, target, w_cce, w_dice):
         """channel softmax + w_cce*categorical_crossentropy + w_dice*dice_loss (target = class index per pixel)."""
         if logits.C < 2:
@@ -1846,7 +1872,8 @@ class Plan(object):
         self.run(self.fwd[k:])
 
     # loss launches whose third argument is the element / pixel count of the batch ([N, ...] -> the first n_valid samples)
-    LOSS_LAUNCHES = ("stp_sigmoid_bce_dice", "stp_softmax_cce_dice", "stp_prob_bce_dice", "stp_sigmoid_loss_ex", "stp_prob_cce_dice")
+    LOSS_LAUNCHES = ("stp_sigmoid_bce_dice", "stp_softmax_cce_dice", "stp_prob_bce_dice", "stp_sigmoid_loss_ex", "stp_prob_cce_dice",
+                     "stp_sigmoid_multilabel_loss")
 
     def rerun_loss(self, n_valid):
         """Re-evaluates the loss / metric reduction over the first ``n_valid`` samples only (an evaluation batch whose tail

@@ -105,19 +105,29 @@ def _class_head(plan, y, classes):
     return plan.conv("final_conv", y, classes, 3, pad=1, bias=True)
 
 
-def _head(plan, x, H, W, classes, loss, with_loss):
+def _loss(plan, logits, target, classes, loss, multilabel):
+    """The head's loss: 1-class sigmoid, multi-label sigmoid (``multilabel``: C = 2..8 sigmoids, target = class bits per pixel)
+    or C-class softmax."""
+    if classes == 1:
+        plan.sigmoid_loss(logits, target, *loss)
+    elif multilabel:
+        if len(loss) > 5 and loss[5]:
+            raise ValueError("lovasz_loss is not available for a multi-label head")
+        plan.sigmoid_multilabel_loss(logits, target, *loss[:5])
+    else:
+        plan.softmax_loss(logits, target, loss[0], loss[1])
+
+
+def _head(plan, x, H, W, classes, loss, with_loss, multilabel=False):
     logits = plan.conv("final_conv", x, classes, 3, pad=1, bias=True)
     if with_loss:
-        target = plan.input_u8("mask", H, W, 1)       # {0,1} for the sigmoid head, class index for the softmax head
-        if classes == 1:
-            plan.sigmoid_loss(logits, target, *loss)
-        else:
-            plan.softmax_loss(logits, target, loss[0], loss[1])
+        target = plan.input_u8("mask", H, W, 1)       # {0,1} for the sigmoid head, class bits (multi-label) or class index (softmax)
+        _loss(plan, logits, target, classes, loss, multilabel)
     return logits
 
 
 def unet_resnet(plan, backbone, H, W, in_ch=3, classes=1, decoder_filters=(256, 128, 64, 32, 16),
-                loss=(1.0, 1.0), with_loss=True, decoder_block_type="upsampling"):
+                loss=(1.0, 1.0), with_loss=True, decoder_block_type="upsampling", multilabel=False):
     """Declares inputs 'image' (uint8 NHWC) and 'mask' (uint8 NHW1); returns the logits tensor.
     ``decoder_block_type``: 'upsampling' (UpSampling2D + concat + 2 x conv3x3) or 'transpose' (Conv2DTranspose 4x4 s2 ->
     BN -> ReLU -> concat -> conv3x3; segmentation_models' Transpose2D_block, schemas/segmentation.raml:166-169)."""
@@ -138,11 +148,11 @@ def unet_resnet(plan, backbone, H, W, in_ch=3, classes=1, decoder_filters=(256, 
         x = plan.bn(pre + "bn1", x, BN_EPS_DECODER, relu=True)
         x = plan.conv(pre + "conv2", x, f, 3, pad=1, bn_stats=True)
         x = plan.bn(pre + "bn2", x, BN_EPS_DECODER, relu=True)
-    return _head(plan, x, H, W, classes, loss, with_loss)
+    return _head(plan, x, H, W, classes, loss, with_loss, multilabel)
 
 
 def linknet_resnet(plan, backbone, H, W, in_ch=3, classes=1, decoder_filters=(None, None, None, None, 16),
-                   loss=(1.0, 1.0), with_loss=True, decoder_block_type="upsampling"):
+                   loss=(1.0, 1.0), with_loss=True, decoder_block_type="upsampling", multilabel=False):
     """segmentation_models 0.2.1 ``Linknet(decoder_use_batchnorm=True)`` (``schemas/segmentation.raml:180-203``): per decoder
     stage 1x1 conv to in/4, then UpSampling2D(2) folded into the 3x3 conv's gather ('upsampling') or Conv2DTranspose 4x4 s2
     ('transpose', ``schemas/segmentation.raml:166-169``), 1x1 conv to the skip's channels, each followed by BN+ReLU, then
@@ -166,11 +176,11 @@ def linknet_resnet(plan, backbone, H, W, in_ch=3, classes=1, decoder_filters=(No
         x = plan.bn(pre + "bn3", plan.conv(pre + "conv3", x, out, 1, bn_stats=True), BN_EPS_DECODER, relu=True)
         if skips[i] is not None:
             x = plan.add(pre + "add", x, skips[i])
-    return _head(plan, x, H, W, classes, loss, with_loss)
+    return _head(plan, x, H, W, classes, loss, with_loss, multilabel)
 
 
 def fpn_resnet(plan, backbone, H, W, in_ch=3, classes=1, decoder_filters=None, loss=(1.0, 1.0), with_loss=True,
-               pyramid_block_filters=256, segmentation_block_filters=128, last_upsample=4, dropout=None, interpolation="bilinear"):
+               pyramid_block_filters=256, segmentation_block_filters=128, last_upsample=4, dropout=None, interpolation="bilinear", multilabel=False):
     """segmentation_models 0.2.1 ``FPN(..., upsample_rates=(2,2,2), interpolation='bilinear', use_batchnorm=True)``
     (``schemas/segmentation.raml:180-203``).  Pyramid over [encoder output, stage4/3/2 unit1 relu1]: 1x1 lateral conv (+ the
     2x nearest upsampling of the level above), two conv3x3+BN+ReLU segmentation convs per level; the four maps are resized
@@ -203,12 +213,12 @@ def fpn_resnet(plan, backbone, H, W, in_ch=3, classes=1, decoder_filters=None, l
     logits = plan.resize("logits", lo, 4, nearest=near)
     if with_loss:
         target = plan.input_u8("mask", H, W, 1)
-        (plan.sigmoid_loss if classes == 1 else plan.softmax_loss)(logits, target, *loss)
+        _loss(plan, logits, target, classes, loss, multilabel)
     return logits
 
 
 def pspnet_resnet(plan, backbone, H, W, in_ch=3, classes=1, decoder_filters=None, loss=(1.0, 1.0), with_loss=True,
-                  downsample_factor=8, psp_conv_filters=512, dropout=None, final_interpolation="bilinear", psp_pooling_type="avg"):
+                  downsample_factor=8, psp_conv_filters=512, dropout=None, final_interpolation="bilinear", psp_pooling_type="avg", multilabel=False):
     """segmentation_models 0.2.1 ``PSPNet(downsample_factor=8, psp_conv_filters=512, psp_pooling_type='avg', use_batchnorm=True,
     final_interpolation='bilinear')`` (``schemas/segmentation.raml:225-249``): the backbone is cut at the 1/8 feature
     (stage3_unit1_relu1; 1/4: stage2, 1/16: stage4); pyramid pooling levels 1, 2, 3, 6 = AveragePooling2D(size/level) ->
@@ -258,7 +268,7 @@ def pspnet_resnet(plan, backbone, H, W, in_ch=3, classes=1, decoder_filters=None
     logits = plan.resize("logits", lo, int(downsample_factor), nearest=final_interpolation == "nearest")
     if with_loss:
         target = plan.input_u8("mask", H, W, 1)
-        (plan.sigmoid_loss if classes == 1 else plan.softmax_loss)(logits, target, *loss)
+        _loss(plan, logits, target, classes, loss, multilabel)
     return logits
 
 

@@ -361,7 +361,7 @@ class TransformAugmentor(object):
         spec = cfg._aug_spec() if self.train else augment.resolve_paths(
             cfg.transforms, os.path.dirname(os.path.abspath(cfg.path)) if cfg.path else None)
         self.feeder = DeviceFeeder(self.device, (self.H, self.W), spec, seed=cfg.random_state if seed is None else seed,
-                                   classes=cfg.classes, channels=self.ch)
+                                   classes=cfg.classes, channels=self.ch, activation=cfg.all.get("activation"))
 
     def augment_batches(self, batches):
         for b in batches:
@@ -431,10 +431,30 @@ class HostItem(object):
         self.id, self.x, self.y, self.h, self.w, self.src = ident, x, y, h, w, src
 
 
-def prepare_item(it, classes, pin, channels=3):
+def is_multilabel(classes, activation):
+    """``classes: C > 1`` with ``activation: sigmoid``: C independent {0,1} maps per image (H x W x C masks)."""
+    return int(classes) > 1 and activation == "sigmoid"
+
+
+def pack_multilabel(y, classes):
+    """H x W x C mask -> uint8 [h, w] with bit c set where y[..., c] != 0 (the target of stp_sigmoid_multilabel_loss).  The
+    augmentation resamples masks by nearest neighbour with a constant-0 border, so the packed bits survive every augmenter."""
+    if not 2 <= classes <= 8:
+        raise ValueError("a multi-label mask packs 2..8 classes into one byte per pixel, not %d" % classes)
+    if y.shape[2] != classes:
+        raise ValueError("a multi-label head of %d classes needs an H x W x %d mask (one {0,1} map per class), got %d channel(s): "
+                         "a single-channel mask cannot say which classes overlap" % (classes, classes, y.shape[2]))
+    out = np.zeros(y.shape[:2], np.uint8)
+    for c in range(classes):
+        out |= (y[:, :, c] != 0).astype(np.uint8) << np.uint8(c)
+    return out
+
+
+def prepare_item(it, classes, pin, channels=3, activation=None):
     """PredictionItem -> HostItem: uint8 pixels [h,w,channels] (RGB, or the first ``channels`` <= 7 bands of an N-channel image:
     ``shape: [H, W, C]`` in the YAML, reference segmentation.py:135-155) and label uint8 [h,w] ({0,1} for the sigmoid head, class
-    index for the softmax head; one-hot maps are arg-maxed).  This is the CPU work per sample; everything else happens on the GPU."""
+    index for the softmax head - one-hot maps are arg-maxed -, class bits for a multi-label sigmoid head: ``activation="sigmoid"``
+    with ``classes > 1``, see pack_multilabel).  This is the CPU work per sample; everything else happens on the GPU."""
     x = np.asarray(it.x)
     if x.ndim == 2:
         x = x[:, :, None]
@@ -450,6 +470,8 @@ def prepare_item(it, classes, pin, channels=3):
     y = np.asarray(y).reshape(h, w, -1)
     if classes == 1:
         y = (y[:, :, 0] != 0).astype(np.uint8)
+    elif is_multilabel(classes, activation):
+        y = pack_multilabel(y, classes)
     elif y.shape[2] == classes:            # one-hot maps (what a Keras softmax head is fed) -> class index
         y = y.argmax(axis=2).astype(np.uint8)
     else:                                  # label image
@@ -481,7 +503,7 @@ class HostPrefetcher(object):
     GPU trains on the current one - the replacement of the reference's imgaug worker processes + bounded queue
     (FAQ.md:15-22; ``AUGMENTER_QUEUE_LIMIT``), minus the augmentation itself, which runs on the device."""
 
-    def __init__(self, ds, indexes, batch, classes, pin, depth=2, sampler=None, channels=3):
+    def __init__(self, ds, indexes, batch, classes, pin, depth=2, sampler=None, channels=3, activation=None):
         """``sampler(n, h, w) -> (batch passes, per-image passes)`` (augment.sample_batch_staged): when given and a batch's items
         share one size, the thread also packs the batch into two pinned blocks and samples its augmentation passes (HostBatch)."""
         import queue
@@ -504,7 +526,8 @@ class HostPrefetcher(object):
         def work():
             try:
                 for s in range(0, len(indexes), batch):
-                    self.q.put(pack([prepare_item(ds[int(i)], classes, False if sampler is not None else pin, channels)
+                    self.q.put(pack([prepare_item(ds[int(i)], classes, False if sampler is not None else pin, channels,
+                                                  activation)
                                      for i in indexes[s:s + batch]]))
             except BaseException as e:      # surfaced on the consumer side
                 self._err = e
@@ -528,8 +551,9 @@ class DeviceFeeder(object):
     stream (they overlap the previous step's kernels), then one ``stp_augment_u8`` launch per item on the compute stream
     that resizes to the network shape and augments when training (+ ``stp_filter_u8`` passes for neighbourhood filters)."""
 
-    def __init__(self, device, out_hw, spec, seed, classes=1, channels=3):
+    def __init__(self, device, out_hw, spec, seed, classes=1, channels=3, activation=None):
         self.device, self.out_hw, self.spec, self.classes = torch.device(device), out_hw, spec, int(classes)
+        self.activation = activation           # the head's activation: "sigmoid" with classes > 1 = multi-label masks
         self.channels = int(channels)          # image channels of the network input (3, or 4..7 for N-channel models)
         self.rng = np.random.RandomState(seed)
         self.pin = self.device.type == "cuda"
@@ -543,7 +567,8 @@ class DeviceFeeder(object):
         oh, ow = self.out_hw
         if isinstance(items, HostBatch) and items.X.shape[0] == n:
             return self._feed_block(plan, items)
-        items = [it if isinstance(it, HostItem) else prepare_item(it, self.classes, self.pin, self.channels) for it in items]
+        items = [it if isinstance(it, HostItem) else prepare_item(it, self.classes, self.pin, self.channels, self.activation)
+                 for it in items]
         ch = self.channels
         main = torch.cuda.current_stream()
         staged = []
@@ -641,21 +666,29 @@ def _feed_block(self, plan, hb):
 DeviceFeeder._feed_block = _feed_block
 
 
-def derived_metrics(scal, classes=1, extended=False):
+def derived_metrics(scal, classes=1, extended=False, activation=None):
     """scal: the loss scalars of stp_sigmoid_bce_dice -> Keras-style log entries (metric names of
     schemas/segmentation.raml:98-105: binary_accuracy, dice, iou, iot).  ``extended``: the loss names one of the other registry
     entries (stp_sigmoid_loss_ex / stp_lovasz_hinge leave them in scalars 10..12): they are logged too, so that
-    ``primary_metric: val_focal_loss`` or a callback monitoring it sees the quantity it names."""
+    ``primary_metric: val_focal_loss`` or a callback monitoring it sees the quantity it names.  The names follow the head's
+    activation: a multi-label sigmoid head (``activation="sigmoid"``, classes > 1) logs binary_crossentropy and has no lovasz_loss."""
     loss, bce, dice_l, dice_m, acc, _sp, _sy, _spy, iou, iot = (float(v) for v in scal[:10])
-    out = {"loss": loss, ("binary_crossentropy" if classes == 1 else "categorical_crossentropy"): bce, "dice_loss": dice_l,
+    multilabel = is_multilabel(classes, activation)
+    out = {"loss": loss, ("binary_crossentropy" if classes == 1 or multilabel else "categorical_crossentropy"): bce, "dice_loss": dice_l,
            "dice": dice_m, "binary_accuracy": acc, "iou": iou, "iot": iot}
     if extended and len(scal) >= 13:
-        out.update(iou_loss=1.0 - iou, jaccard_loss=float(scal[10]), focal_loss=float(scal[11]), lovasz_loss=float(scal[12]))
+        out.update(iou_loss=1.0 - iou, jaccard_loss=float(scal[10]), focal_loss=float(scal[11]))
+        if not multilabel:
+            out["lovasz_loss"] = float(scal[12])
     return out
 
 
 def _extended(model):
     return len(getattr(model, "loss_w", ())) > 2
+
+
+def _activation(model):
+    return getattr(model, "head_activation", None)
 
 
 class Trainer(object):
@@ -675,7 +708,8 @@ class Trainer(object):
         # training thread's draws (per-item path of DeviceFeeder.feed, DrawResults) never interleave with it
         rng = np.random.RandomState(f.rng.randint(0, 2 ** 31 - 1))
         sampler = lambda n, h, w: augment.sample_batch_staged(f.spec if training else [], rng, n, h, w, oh_ow)
-        return HostPrefetcher(self.ds, [int(i) for i in indexes], batch, f.classes, f.pin, sampler=sampler, channels=f.channels)
+        return HostPrefetcher(self.ds, [int(i) for i in indexes], batch, f.classes, f.pin, sampler=sampler, channels=f.channels,
+                              activation=getattr(f, "activation", None))
 
     def run_epoch_sums(self, indexes, training):
         """One pass over ``indexes`` -> ({log name: sum over batches of value * real samples of the batch}, real samples).
@@ -730,7 +764,7 @@ class Trainer(object):
         sums = {}
         if snaps:
             for scal, n in zip(torch.stack(snaps).cpu().numpy(), counts):
-                for k, v in derived_metrics(scal, getattr(m, "classes", 1), _extended(m)).items():
+                for k, v in derived_metrics(scal, getattr(m, "classes", 1), _extended(m), _activation(m)).items():
                     sums[k] = sums.get(k, 0.0) + v * n
         return sums, int(sum(counts))
 
@@ -738,17 +772,17 @@ class Trainer(object):
         """Sample-weighted epoch means, combined over all ranks (one small SUM-all-reduce per call): every rank returns
         the same values bit for bit."""
         sums, n = self.run_epoch_sums(indexes, training)
-        return reduce_epoch_sums(sums, n, getattr(self.model, "classes", 1), _extended(self.model))
+        return reduce_epoch_sums(sums, n, getattr(self.model, "classes", 1), _extended(self.model), _activation(self.model))
 
 
-def epoch_log_names(classes=1, extended=False):
-    return sorted(derived_metrics(np.zeros(16, np.float32), classes, extended))
+def epoch_log_names(classes=1, extended=False, activation=None):
+    return sorted(derived_metrics(np.zeros(16, np.float32), classes, extended, activation))
 
 
-def reduce_epoch_sums(sums, n, classes=1, extended=False):
+def reduce_epoch_sums(sums, n, classes=1, extended=False, activation=None):
     """{name: weighted sum}, samples -> {name: mean over the samples of ALL ranks}.  The vector layout is fixed by the
     metric names (not by what a rank happened to see), so a rank with an empty shard still takes part in the collective."""
-    names = epoch_log_names(classes, extended)
+    names = epoch_log_names(classes, extended, activation)
     vec = distributed.allreduce_sums([sums.get(k, 0.0) for k in names] + [float(n)])
     total = vec[-1]
     if total <= 0:
@@ -982,7 +1016,7 @@ class GenericTaskConfig(object):
                 impl.reducer.reset_bounds()
         H, W = impl.H, impl.W                                  # = shape, or shape / crops
         feeder = DeviceFeeder(impl.device, (H, W), self._aug_spec(), seed=self.random_state * 7919 + fold * 101 + si,
-                              classes=self.classes, channels=impl.in_ch)
+                              classes=self.classes, channels=impl.in_ch, activation=getattr(impl, "head_activation", None))
         cbs = stage.callbacks()
         trainer = Trainer(impl, feeder, ds, cbs, rank, world)
         train_idx = kf.sampledIndexes(fold, True, stage.negatives)
@@ -997,7 +1031,7 @@ class GenericTaskConfig(object):
         # primary_metric / callback monitors are checked against the names an epoch will log BEFORE the first epoch trains (a typo used
         # to surface only after a whole epoch: advisor finding, round 3)
         known = {}
-        for k in epoch_log_names(self.classes, _extended(impl)) + ["lr"]:
+        for k in epoch_log_names(self.classes, _extended(impl), _activation(impl)) + ["lr"]:
             known[k] = 0.0
             known["val_" + k] = 0.0
         for what, name in [("primary_metric", self.primary_metric)] + [("%s.monitor" % type(cb).__name__, cb.monitor) for cb in cbs if hasattr(cb, "monitor")]:
@@ -1073,7 +1107,8 @@ class GenericTaskConfig(object):
         model = self._compiled(st)
         impl = model.impl
         H, W = impl.H, impl.W                                  # = shape, or shape / crops: the size of the plan's input buffers
-        feeder = DeviceFeeder(impl.device, (H, W), self._aug_spec(), seed=self.random_state, classes=self.classes, channels=impl.in_ch)
+        feeder = DeviceFeeder(impl.device, (H, W), self._aug_spec(), seed=self.random_state, classes=self.classes, channels=impl.in_ch,
+                              activation=getattr(impl, "head_activation", None))
         trainer = Trainer(impl, feeder, d, [], 0, 1)
         nb = max(1, -(-len(idx) // impl.batch)) * int(epochs)
         finder = LRFinder(float(start_lr), float(end_lr), nb)
