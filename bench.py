@@ -3,15 +3,19 @@
 
 DEFAULT (--config 1, what the driver runs) = BASELINE.json configs[1]: U-Net/ResNet-34, 512x512x3 -> 1 class, batch 16 per GPU, bf16
 MFMA; configs[2] = the same with --gpus 8.  --config 3 = configs[3]: FPN/ResNet-50 1024x1024 3-class batch 4, fp16 MFMA;
---config 4 = configs[4]: PSPNet/ResNet-101 768x768 20-class batch 8, bf16, heavy augmentation.  Same JSON shape
-for every config (roofline, roofline_hbm, step_traffic_gb, kernel_time_us, cpu_baseline, box_calibration).
+--config 4 = configs[4]: PSPNet/ResNet-101 768x768 20-class batch 8, bf16, heavy augmentation.
 
 One "step" = on-device augmentation of the resident uint8 batch + weight compute copies + forward + loss (sigmoid BCE + Dice, or
 softmax CCE + Dice) + backward + (RCCL gradient all-reduce when N > 1) + Adam.  Raw images and masks are resident in HBM before the
 timed region.  Prints ONE JSON line on rank 0.
 
+A plain run does only what the headline figure needs: set-up, the warm-up and the counted steps, --dump-outputs, the line.  --full adds
+every other measurement and check, the same JSON shape for every config: box_calibration before the timed region, the network alone
+(configs 3 / 4), the step fed from pinned host memory, the sustained region, the per-kernel table and rooflines (roofline, roofline_hbm,
+step_traffic_gb, kernel_time_us), the Dice delta against the oracle and the CPU baseline (--no-* / --sustain / --cpu-baseline trim it).
+
     python bench.py --gpus 1 --steps 20 --warmup 5
-    python bench.py --config 4 --cpu-baseline short
+    python bench.py --full --config 4 --cpu-baseline short
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29511 \
         bench.py --gpus 8 --steps 20 --warmup 5
 """
@@ -579,18 +583,21 @@ def main():
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp16", "fp32"],
                     help="default: the precision BASELINE.json names for the config (bf16 / fp16 / bf16).  bf16 = libstp_hip.so; fp16 = the "
                          "IEEE-half build of the same kernels (libstp_hip_f16.so, loss scale 2^14); fp32 = the parity mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, measure and check everything else (module docstring); the options marked --full "
+                         "below trim such a run and do nothing without it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the Dice delta against the oracle")
     ap.add_argument("--cpu-baseline", default="full", choices=["full", "short"],
-                    help="config 1: full = BASELINE.md 4 as written (batch 16, 3 warm-up + 10 timed steps: ~5 min of host time); short = 1 + 3.  "
+                    help="--full, config 1: full = BASELINE.md 4 as written (batch 16, 3 warm-up + 10 timed steps: ~5 min of host time); short = 1 + 3.  "
                          "configs 3 / 4: full = 1 + 4 steps of the config's batch, short = 1 + 2")
-    ap.add_argument("--no-kernel-profile", action="store_true")
-    ap.add_argument("--no-calibration", action="store_true", help="skip the ~2.5 s box calibration (MFMA rate + copy bandwidth) before the timed region")
+    ap.add_argument("--no-kernel-profile", action="store_true", help="--full: skip the instrumented per-kernel passes and the rooflines")
+    ap.add_argument("--no-calibration", action="store_true", help="--full: skip the ~2.5 s box calibration (MFMA rate + copy bandwidth) before the timed region")
     ap.add_argument("--architecture", default=None, choices=["Unet", "Linknet", "FPN"],
                     help="config 1 only: Linknet / FPN over ResNet34 on the same shapes (SURVEY 8f N1 workloads, not the headline metric)")
     ap.add_argument("--eager", action="store_true", help="no hipGraph (for rocprofv3 kernel traces of the launches themselves)")
-    ap.add_argument("--no-feed", action="store_true", help="skip the region fed from pinned host memory (profiler traces of the resident step only)")
+    ap.add_argument("--no-feed", action="store_true", help="--full: skip the region fed from pinned host memory (profiler traces of the resident step only)")
     ap.add_argument("--sustain", type=float, default=8.0,
-                    help="seconds of extra back-to-back steps after the counted ones, reported as `sustained` (0 = skip; 1-GPU runs only)")
+                    help="--full: seconds of extra back-to-back steps after the counted ones, reported as `sustained` (0 = skip; 1-GPU runs only)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the --steps counted steps (before any other region), write what the last of them computed to DIR/<name>.npy "
                          "(rank 0): metrics, logits, updated weights and BatchNormalization statistics, at most 64 MB in all")
@@ -623,8 +630,8 @@ def main():
     distributed.init(os.environ.get("STP_DIST_BACKEND") or "nccl", force=force_dp)
     dev = torch.device("cuda", dev_index)
 
-    # what this box sustains on two fixed loads (rank 0, before anything else runs on the device)
-    calib = box_calibration(dev) if (rank == 0 and not args.no_calibration) else None
+    # what this box sustains on two fixed loads (--full, rank 0, before anything else runs on the device)
+    calib = box_calibration(dev) if (args.full and rank == 0 and not args.no_calibration) else None
     if world > 1:
         dist.barrier()
 
@@ -715,10 +722,10 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(model, args.dump_outputs)              # (the regions below train on: their steps are not the counted ones)
 
-    # ---- the network alone (no augmentation launch): the part of the step the launch tables / floor tables describe.  Configs 3 / 4 only
-    # (config 1 keeps its established region list); the batch in the plan's input buffers is the last augmented one
+    # ---- the network alone (no augmentation launch): the part of the step the launch tables / floor tables describe.  --full, configs 3 / 4
+    # only (config 1 keeps its established region list); the batch in the plan's input buffers is the last augmented one
     elapsed_model = None
-    if args.config != 1 and not overlap:
+    if args.full and args.config != 1 and not overlap:
         elapsed_model = timed(lambda i: model.train_on_batch(None, None, fetch=False), 0, args.steps)
 
     # ---- the same step FED from pinned host memory (north_star: "fed by pinned hipMemcpyAsync"): NHOST distinct raw batches in pinned
@@ -729,63 +736,64 @@ def main():
     # enqueued only if the host-side query says the copy is still running).  Measured (profiles/r04n_feed_experiments.txt): with two
     # buffers and event waits both ways the fed step cost +0.42 ms although the copies themselves (228 + 81 us on the SDMA engine) cost
     # nothing (+0.03 ms without the waits): a cross-stream dependency next to a hipGraph launch costs ~0.1 ms on this runtime.
-    # Reported next to the resident number (`value` stays the resident one, as the bench contract prescribes).
-    NHOST, NBUF = 4, 3
-    h_img = [torch.from_numpy(np.roll(img, k, axis=0).copy()).pin_memory() for k in range(NHOST)]
-    h_msk = [torch.from_numpy(np.roll(msk, k, axis=0).copy()).pin_memory() for k in range(NHOST)]
-    d_img = [torch.empty_like(raw_img) for _ in range(NBUF)]
-    d_msk = [torch.empty_like(raw_msk) for _ in range(NBUF)]
-    copy_stream = torch.cuda.Stream(device=dev)
-    ready = [torch.cuda.Event() for _ in range(NBUF)]
-    step_done = [torch.cuda.Event() for _ in range(NBUF)]
-
-    def stage(i):
-        b = i % NBUF
-        with torch.cuda.stream(copy_stream):
-            d_img[b].copy_(h_img[i % NHOST], non_blocking=True)
-            d_msk[b].copy_(h_msk[i % NHOST], non_blocking=True)
-            ready[b].record(copy_stream)
-
-    def feed_into_plan(i, stream):
-        b = i % NBUF
-        if not ready[b].query():
-            stream.wait_event(ready[b])                   # (not in steady state: the copy was issued a step ago)
-        augment_into_plan(d_img[b], d_msk[b], i)
-
-    def step_fed(i):
-        main = torch.cuda.current_stream()
-        step_done[(i - 2) % NBUF].synchronize()           # host throttle: step i - 2 has finished => staging buffer (i + 1) % 3 is free
-        stage(i + 1)
-        if not overlap:
-            feed_into_plan(i, main)
-            model.train_on_batch(None, None, fetch=False)
-        else:
-            model.forward_backward()
-            aux.wait_stream(main)
-            with torch.cuda.stream(aux):
-                feed_into_plan(i + 1, aux)
-            model.apply_gradients()
-            main.wait_stream(aux)
-        step_done[i % NBUF].record(main)
-
-    torch.cuda.synchronize()
-    for b in range(NBUF):
-        step_done[b].record(torch.cuda.current_stream())
-    stage(0)
-    if overlap:
-        stage(1)
-        feed_into_plan(0, torch.cuda.current_stream())
+    # Reported next to the resident number (`value` stays the resident one, as the bench contract prescribes).  --full only.
     elapsed_fed = None
-    if not args.no_feed:
-        for i in range(2):
-            step_fed(i)
-        elapsed_fed = timed(step_fed, 2, args.steps)
-    torch.cuda.synchronize()
+    if args.full:
+        NHOST, NBUF = 4, 3
+        h_img = [torch.from_numpy(np.roll(img, k, axis=0).copy()).pin_memory() for k in range(NHOST)]
+        h_msk = [torch.from_numpy(np.roll(msk, k, axis=0).copy()).pin_memory() for k in range(NHOST)]
+        d_img = [torch.empty_like(raw_img) for _ in range(NBUF)]
+        d_msk = [torch.empty_like(raw_msk) for _ in range(NBUF)]
+        copy_stream = torch.cuda.Stream(device=dev)
+        ready = [torch.cuda.Event() for _ in range(NBUF)]
+        step_done = [torch.cuda.Event() for _ in range(NBUF)]
 
-    # ---- a LONG region of the resident step (world 1 only): the 20 counted steps last 0.15 s, which a 5 s utilisation sampler
+        def stage(i):
+            b = i % NBUF
+            with torch.cuda.stream(copy_stream):
+                d_img[b].copy_(h_img[i % NHOST], non_blocking=True)
+                d_msk[b].copy_(h_msk[i % NHOST], non_blocking=True)
+                ready[b].record(copy_stream)
+
+        def feed_into_plan(i, stream):
+            b = i % NBUF
+            if not ready[b].query():
+                stream.wait_event(ready[b])                   # (not in steady state: the copy was issued a step ago)
+            augment_into_plan(d_img[b], d_msk[b], i)
+
+        def step_fed(i):
+            main = torch.cuda.current_stream()
+            step_done[(i - 2) % NBUF].synchronize()           # host throttle: step i - 2 has finished => staging buffer (i + 1) % 3 is free
+            stage(i + 1)
+            if not overlap:
+                feed_into_plan(i, main)
+                model.train_on_batch(None, None, fetch=False)
+            else:
+                model.forward_backward()
+                aux.wait_stream(main)
+                with torch.cuda.stream(aux):
+                    feed_into_plan(i + 1, aux)
+                model.apply_gradients()
+                main.wait_stream(aux)
+            step_done[i % NBUF].record(main)
+
+        torch.cuda.synchronize()
+        for b in range(NBUF):
+            step_done[b].record(torch.cuda.current_stream())
+        stage(0)
+        if overlap:
+            stage(1)
+            feed_into_plan(0, torch.cuda.current_stream())
+        if not args.no_feed:
+            for i in range(2):
+                step_fed(i)
+            elapsed_fed = timed(step_fed, 2, args.steps)
+        torch.cuda.synchronize()
+
+    # ---- a LONG region of the resident step (--full, world 1 only): the 20 counted steps last 0.15 s, which a 5 s utilisation sampler
     # misses entirely; ~8 s of back-to-back replays give an independent observer something to see, and a drift-free average
     sustained = None
-    if world == 1 and args.sustain > 0:
+    if args.full and world == 1 and args.sustain > 0:
         n_sus = max(200, int(args.sustain / max(elapsed / args.steps, 1e-4)))
         with ClockSampler(dev_index) as clocks:
             sustained = (n_sus, timed(step, 0, n_sus))
@@ -819,7 +827,7 @@ def main():
                             "images_per_sec": round(BATCH * sustained[0] / sustained[1], 2),
                             # shader clock / socket power the box held over this region (amdgpu hwmon, 50 ms samples; None: not readable)
                             "clocks": sustained_clocks}
-    if rank == 0 and not args.no_kernel_profile:
+    if args.full and rank == 0 and not args.no_kernel_profile:
         prof = per_kernel_profile(model)
         tot = sum(v[1] for v in prof.values())
         gemm = {k: v for k, v in prof.items() if v[2] > 0}
@@ -875,7 +883,7 @@ def main():
         out["kernel_time_total_us"] = round(1e6 * tot, 1)
         out["gemm_time_us"] = round(1e6 * sum(v[1] for v in gemm.values()), 1)
         out["non_gemm_time_us"] = round(1e6 * (tot - sum(v[1] for v in gemm.values())), 1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if args.dtype == "bf16" and arch == "Unet" and args.config == 1:
             out["config"]["dice_delta_vs_oracle"] = dice_delta_vs_oracle(str(dev))
         if arch == cfg["architecture"]:

@@ -6,5 +6,5 @@ python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke
 bash scratch/r06/prof_r06.sh $T 1 full
 bash scratch/r06/prof_r06.sh $T 3 short
 bash scratch/r06/prof_r06.sh $T 4 short
-python bench.py --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_100steps.json 2> $O/bench_100steps.err
+python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_100steps.json 2> $O/bench_100steps.err
 ls $O | head -60

@@ -21,8 +21,8 @@ python scratch/pmc_aggregate_sq.py $(find $O/pmc_sq$SUF -name "*counter_collecti
 mkdir -p $R/profiles
 cp $O/pmc_traffic$SUF.json $R/profiles/${T}_pmc_traffic$SUF.json
 cp $O/pmc_sq$SUF.json $R/profiles/${T}_pmc_sq$SUF.json
-if [ "$FULL" = "full" ]; then python bench.py --config $CFG > $O/bench_config$CFG.json 2> $O/bench_config$CFG.err
-else python bench.py --config $CFG --cpu-baseline short > $O/bench_config$CFG.json 2> $O/bench_config$CFG.err; fi
+if [ "$FULL" = "full" ]; then python bench.py --full --config $CFG > $O/bench_config$CFG.json 2> $O/bench_config$CFG.err
+else python bench.py --full --config $CFG --cpu-baseline short > $O/bench_config$CFG.json 2> $O/bench_config$CFG.err; fi
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktg$SUF -o kt -- python $R/bench.py --steps 10 --warmup 3 $Q --no-kernel-profile > $O/bench_profiled_graph_only$SUF.json 2> $O/ktg$SUF.err
 cd $R
