@@ -3091,12 +3091,14 @@ __global__ __launch_bounds__(256) void maxpool_k_kernel(const T* __restrict__ x,
     const int64_t p = i / C;
     const int xo = (int)(p % Wo), yo = (int)((p / Wo) % Ho), n = (int)(p / ((int64_t)Wo * Ho));
     const T* b = x + (((int64_t)n * H + yo * k) * W + xo * k) * C + c;
-    float best = -3.4e38f;
+    // the running maximum starts from the window's first element, not from a finite floor: a window of -inf (or of fp32 values below
+    // the floor) pools to its own maximum with idx 0, as MaxPooling2D does
+    float best = 0.f;
     int bi = 0;
     for (int a = 0; a < k; ++a)
       for (int q = 0; q < k; ++q) {
         const float v = Elem<T>::load(b + ((int64_t)a * W + q) * C);
-        if (v > best) { best = v; bi = a * k + q; }
+        if ((a | q) == 0 || v > best) { best = v; bi = a * k + q; }
       }
     Elem<T>::store(y + i, best);
     if (idx) idx[i] = bi;

@@ -685,7 +685,15 @@ extern "C" int stp_conv2d_tile_for(const stp_conv_params* p) {
   return tile;
 }
 
-extern "C" size_t stp_conv2d_stats_floats(const stp_conv_params* p) {
+// Whoever asks for the size of the table wants statistics, and asks BEFORE the table exists (graph.Plan.conv sets stats_partial after the
+// allocation): the selectors are evaluated on a copy that carries a non-null table marker (never dereferenced by a query), so the answer
+// is the one of the launch that follows with the pointer set, whatever the pointer holds at the time of the query.
+extern "C" size_t stp_conv2d_stats_floats(const stp_conv_params* p_) {
+  if (!p_) return 0;
+  static float table_marker;
+  stp_conv_params with_table = *p_;
+  if (!with_table.stats_partial) with_table.stats_partial = &table_marker;
+  const stp_conv_params* p = &with_table;
   const int tile = stp_conv2d_tile_for(p);
   if (tile < 0) return 0;
   if (tile == STP_TILE_SC) return (size_t)stp_conv2d_sc_stats_tiles(p) * 2 * p->Cout;

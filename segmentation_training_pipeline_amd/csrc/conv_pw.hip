@@ -311,8 +311,12 @@ extern "C" int stp_conv2d_pw_eligible(const stp_conv_params* p) {
   if (!c) return 0;
   const int64_t P = (int64_t)p->N * p->Ho * p->Wo;
   if (P % c->tp || P * p->C0 * 2 >= (1ll << 31) || P * p->Cout * 2 >= (1ll << 31)) return 0;
-  // (stats_partial may still be NULL here: the sizing queries - stp_conv2d_stats_floats - run before the table is allocated, and must
-  //  give the answer of the launch that follows; a BatchNormalization-backward launch without its table is refused by stp_conv2d_pw)
+  // This is the only selector that reads the table pointer: a launch WITH fused statistics has no bias / accumulate epilogue here, one
+  // without has.  It answers for the parameters it is given - the launch (stp_conv2d) and stp_conv2d_tile_for see the pointer as set by
+  // the caller.  The sizing query, which runs before the table is allocated, does not rely on that: stp_conv2d_stats_floats evaluates
+  // every selector on a copy with a non-null table marker, so it sizes for the kernel the launch with the table takes
+  // (tests/test_host.py::test_stats_sizing_query_does_not_depend_on_the_table_pointer).  A BatchNormalization-backward launch always
+  // has statistics; one without its table is refused by stp_conv2d_pw.
   const bool bnb = p->bnb_x != nullptr, stats = p->stats_partial != nullptr || bnb;
   if (bnb && (!p->bnb_mean || !p->bnb_rstd || p->residual || p->bias)) return 0;
   if (bnb && pw_bnb_level(c->cin, c->cout) < (p->accumulate0 ? 2 : 1)) return 0;

@@ -658,6 +658,7 @@ extern "C" int stp_prob_cce_dice(const void* probs, const uint8_t* target, int64
                                  void* stream) {
   if (!stp_dtype_ok(dtype)) return STP_E_BADARG;      // (the other build's 16-bit code, or garbage)
   if (!probs || !target || !scalars || !workspace || pixels <= 0 || classes < 2 || classes > 32 || ldc < classes) return STP_E_BADARG;
+  if (dprobs && dl_channels < classes) return STP_E_BADARG;      // (refused before anything is launched)
   if (workspace_bytes < (size_t)PL_MAX_BLOCKS * PL_NSUM * sizeof(float)) return STP_E_WORKSPACE;
   if (dtype != STP_H16 && dtype != STP_F32) return STP_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
@@ -673,7 +674,6 @@ extern "C" int stp_prob_cce_dice(const void* probs, const uint8_t* target, int64
                      w_dice, scalars);
   STP_LAUNCH_CHECK();
   if (dprobs) {
-    if (dl_channels < classes) return STP_E_BADARG;
     const int g = dl_grid(pixels);
     if (dtype == STP_H16) hipLaunchKernelGGL(prob_cce_grad_kernel<bf16_t>, dim3(g), dim3(256), 0, s, (const bf16_t*)probs, target, pixels, classes, ldc, scalars, w_cce, w_dice, (float)(1.0 / (double)pixels), (bf16_t*)dprobs, dl_channels);
     else hipLaunchKernelGGL(prob_cce_grad_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)probs, target, pixels, classes, ldc, scalars, w_cce, w_dice, (float)(1.0 / (double)pixels), (float*)dprobs, dl_channels);

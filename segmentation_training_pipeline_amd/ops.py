@@ -166,6 +166,55 @@ def maxpool3x3s2_bwd(idx, dy, dx, N, H, W, Cn, accumulate=0):
     _lib.call("stp_maxpool3x3s2_bwd", ptr(idx), ptr(dy), ptr(dx), N, H, W, Cn, dt(dy), int(accumulate), stream())
 
 
+def maxpool2x2(x, y, idx, N, H, W, Cn):
+    _lib.call("stp_maxpool2x2", ptr(x), ptr(y), ptr(idx), N, H, W, Cn, dt(x), stream())
+
+
+def maxpool2x2_bwd(idx, dy, dx, N, H, W, Cn, accumulate=0):
+    _lib.call("stp_maxpool2x2_bwd", ptr(idx), ptr(dy), ptr(dx), N, H, W, Cn, dt(dy), int(accumulate), stream())
+
+
+def maxpool_k(x, y, idx, N, H, W, Cn, k):
+    _lib.call("stp_maxpool_k", ptr(x), ptr(y), ptr(idx), N, H, W, Cn, k, dt(x), stream())
+
+
+def maxpool_k_bwd(idx, dy, dx, N, H, W, Cn, k, accumulate=0):
+    _lib.call("stp_maxpool_k_bwd", ptr(idx), ptr(dy), ptr(dx), N, H, W, Cn, k, dt(dy), int(accumulate), stream())
+
+
+def relu_bwd(y, dy, count):
+    _lib.call("stp_relu_bwd", ptr(y), ptr(dy), count, dt(dy), stream())
+
+
+def zero_bytes(t, nbytes):
+    _lib.call("stp_zero_bytes", ptr(t), nbytes, stream())
+
+
+def resize_nearest(x, y, N, H, W, Cn, factor, ldo, coff):
+    _lib.call("stp_resize_nearest", ptr(x), ptr(y), N, H, W, Cn, factor, ldo, coff, dt(x), stream())
+
+
+def resize_nearest_bwd(dy, dx, N, H, W, Cn, factor, ldo, coff, accumulate=0):
+    _lib.call("stp_resize_nearest_bwd", ptr(dy), ptr(dx), N, H, W, Cn, factor, ldo, coff, dt(dy), int(accumulate), stream())
+
+
+def dropout_spatial(x, y, N, HW, Cn, rate, state, salt):
+    _lib.call("stp_dropout_spatial", ptr(x), ptr(y), N, HW, Cn, float(rate), ptr(state), int(salt), dt(x), stream())
+
+
+def softmax_act(z, p, rows, classes, ldz, ldp):
+    _lib.call("stp_softmax_act", ptr(z), ptr(p), rows, classes, ldz, ldp, dt(z), stream())
+
+
+def softmax_act_bwd(p, dp, dz, rows, classes, ldp, ldg):
+    _lib.call("stp_softmax_act_bwd", ptr(p), ptr(dp), ptr(dz), rows, classes, ldp, ldg, dt(p), stream())
+
+
+def prob_cce_dice(probs, target, pixels, classes, ldc, w_cce, w_dice, scalars, dprobs, dl_channels, workspace):
+    _lib.call("stp_prob_cce_dice", ptr(probs), ptr(target), pixels, classes, ldc, dt(probs), float(w_cce), float(w_dice), ptr(scalars),
+              ptr(dprobs), dl_channels, ptr(workspace), workspace.numel() * workspace.element_size(), stream())
+
+
 def upsample2x_bwd(dy, dx, N, H, W, Cn, ldy, accumulate=0):
     _lib.call("stp_upsample2x_bwd", ptr(dy), ptr(dx), N, H, W, Cn, ldy, dt(dy), int(accumulate), stream())
 

@@ -71,3 +71,42 @@ def test_no_cpu_fallback():
     if not torch.cuda.is_available():
         with pytest.raises(_lib.StpError):
             graph.Plan(2, "bf16", "cuda")
+
+
+# Entry points of include/stp_hip.h that no file under tests/ names (as `stp_<name>` or through its thin wrapper `ops.<name>(`).
+# Everything else the header declares must be named by a test: a kernel added without an op-level test fails
+# test_every_compute_entry_point_is_named_by_a_test.  Only queries, calibration helpers and dispatch targets that the suite
+# reaches through their dispatcher belong here - each with its reason.
+UNNAMED_ENTRY_POINTS = {
+    # calibration micro-kernels of bench.py's roofline (no result to compare: they measure the machine)
+    "stp_calib_mfma_flops": "query: FLOP count of the calibration kernel",
+    "stp_calib_mfma": "calibration: MFMA peak",
+    "stp_calib_copy": "calibration: copy bandwidth",
+    # host-side queries
+    "stp_conv2d_fold_ok": "query: whether the plan may fold a shortcut (exercised through graph.Plan in the step tests)",
+    "stp_wgrad_sc_slabs": "query: slab count of the small-channel weight gradient (read by stp_conv2d_wgrad_workspace_bytes)",
+    "stp_wgrad_group_table_bytes": "query: used by ops.WgradGroup, which the grouped weight-gradient tests construct",
+    "stp_wgrad_group_workspace_bytes": "query: used by ops.WgradGroup",
+    "stp_wgrad_group_build": "host-side table builder: used by ops.WgradGroup",
+    # dispatch targets: the tests reach them through their dispatcher with a forced tile id / an asserted kernel id
+    "stp_conv2d_sc": "stp_conv2d with tile 512 (tests assert stp_conv2d_tile_for == 512)",
+    "stp_conv2d_stem": "stp_conv2d with tile 768",
+    "stp_conv2d_halo": "stp_conv2d with tile 1024 + variant",
+    "stp_wgrad_sc_partial": "stp_conv2d_wgrad_partial variant 0 where stp_wgrad_sc_eligible (tests assert stp_conv2d_wgrad_kernel_id == 1)",
+}
+
+
+def test_every_compute_entry_point_is_named_by_a_test():
+    here = os.path.join(ROOT, "tests")
+    text = ""
+    for f in sorted(os.listdir(here)):
+        if f.endswith(".py"):
+            with open(os.path.join(here, f)) as fh:
+                body = fh.read()
+            if f == "test_abi.py":
+                body = body.split("UNNAMED_ENTRY_POINTS = {")[0]         # (the allow-list itself names nothing)
+            text += body + "\n"
+    unnamed = [n for n in declared_symbols()
+               if not re.search(r"\b%s\b" % n, text) and not re.search(r"\bops\.%s\(" % n[len("stp_"):], text)]
+    assert sorted(unnamed) == sorted(UNNAMED_ENTRY_POINTS), (sorted(set(unnamed) - set(UNNAMED_ENTRY_POINTS)),
+                                                            sorted(set(UNNAMED_ENTRY_POINTS) - set(unnamed)))

@@ -635,6 +635,95 @@ def test_pointwise_kernel_sizing_queries_do_not_depend_on_the_table_pointer():
                 assert t1 == 800 and f1 == 2 * cout * lib.stp_conv2d_pw_cols(C.byref(p)) and 0 < lib.stp_conv2d_pw_cols(C.byref(p)) <= 512
 
 
+def test_stats_sizing_query_does_not_depend_on_the_table_pointer():
+    """stp_conv2d_stats_floats sizes the table of fused sums BEFORE it exists (graph.Plan.conv sets stats_partial after the allocation),
+    so its answer must not change when the pointer is set, and it must be the column count of the kernel that
+    stp_conv2d_tile_for names WITH the pointer set - the one the launch takes.  stp_conv2d_pw_eligible reads the pointer (a launch with
+    fused statistics has no bias / accumulate epilogue on the pointwise kernel): a 1x1 convolution of a served shape with bias or
+    accumulate0 used to be sized for the pointwise kernel (<= 512 columns) and launched on the per-tap kernel (ceil(P / tile) columns) -
+    a device write past the table.  Sweep: every pointwise shape x pixel counts it serves x bias x accumulate0 x residual x
+    BatchNormalization backward x tile 0 / 800, and every convolution of the default step (small-channel, wide / narrow output, stem,
+    halo and per-tap kernels) plus its 64 -> 64 layers under the opt-in tile 736.  Host logic only: runs without a GPU."""
+    import ctypes as C
+    from segmentation_training_pipeline_amd import _lib
+    lib = _lib.load()
+
+    def tile_pixels(tile):                       # conv_igemm.hip: pixels per tile of the per-tap kernels
+        t = tile - 256 if tile >= 256 else tile % 32
+        return 256 if t in (2, 3, 4) else 128 if t in (1, 7) else 64
+
+    def columns(p, tile):                        # of the kernel `tile` names, from the per-kernel queries of include/stp_hip.h
+        ref = C.byref(p)
+        if tile == 800:
+            return lib.stp_conv2d_pw_cols(ref), p.Cout
+        if tile == 512:
+            return lib.stp_conv2d_sc_stats_tiles(ref), p.Cout
+        if tile == 640:
+            return lib.stp_conv2d_scw_stats_tiles(ref), p.Cd0
+        if tile == 704:
+            return lib.stp_conv2d_scn_stats_tiles(ref), p.Cout
+        if tile == 736:
+            return lib.stp_conv2d_s64_stats_tiles(ref), p.Cout
+        if tile == 768:
+            return None, p.Cout                  # (the stem kernel has no public column query: invariance only)
+        if tile >= 1024:
+            return lib.stp_conv2d_halo_tiles(ref, tile - 1024), (p.Cd0 if p.dst_sum2x2 else p.Cout)
+        return -(-(p.N * p.Ho * p.Wo) // tile_pixels(tile)), p.Cout
+
+    seen = {}
+
+    def check(p, what):
+        q = _lib.ConvParams.from_buffer_copy(p)
+        q.stats_partial = None
+        f0 = lib.stp_conv2d_stats_floats(C.byref(q))
+        q.stats_partial = 16                     # (any non-null address: the queries never dereference it)
+        f1, tile = lib.stp_conv2d_stats_floats(C.byref(q)), lib.stp_conv2d_tile_for(C.byref(q))
+        assert f0 == f1, (what, tile, f0, f1)
+        if tile < 0:
+            assert f1 == 0, (what, tile, f1)
+            return tile
+        cols, width = columns(q, tile)
+        assert f1 > 0 and (cols is None or f1 == 2 * width * cols), (what, tile, f1, cols, width)
+        seen[min(tile, 1024) if tile >= 512 else 0] = seen.get(min(tile, 1024) if tile >= 512 else 0, 0) + 1
+        return tile
+
+    pw_pairs = ((64, 64), (64, 256), (256, 64), (256, 128), (128, 256), (128, 512), (512, 128), (256, 256), (512, 256), (256, 512), (64, 512))
+    for (cin, cout) in pw_pairs:
+        for (n, h, w) in ((2, 32, 32), (1, 16, 64), (8, 96, 96)):
+            for bias in (0, 1):
+                for acc in (0, 1):
+                    for res in (0, 1):
+                        for bnb in (0, 1):
+                            for tile in (0, 800):
+                                p = _lib.ConvParams()
+                                p.src0 = p.weight = p.dst0 = 16
+                                p.N, p.Hs0, p.Ws0, p.Hv, p.Wv, p.C0, p.C1 = n, h, w, h, w, cin, 0
+                                p.src0_mode, p.KH, p.KW, p.stride, p.pad, p.Ho, p.Wo, p.Cout, p.Cd0, p.dtype = 0, 1, 1, 1, 0, h, w, cout, cout, _lib.BF16
+                                p.bias, p.residual, p.accumulate0, p.tile = (16 if bias else None), (16 if res else None), acc, tile
+                                if bnb:
+                                    p.bnb_x = p.bnb_mean = p.bnb_rstd = 16
+                                    p.bnb_relu = 1
+                                t = check(p, ((cin, cout), (n, h, w), bias, acc, res, bnb, tile))
+                                if not (bias or acc or res or bnb):
+                                    assert t == 800          # statistics alone: the pointwise kernel serves every shape of the sweep
+                                if (bias or acc) and not bnb:
+                                    assert t != 800          # ... and never together with a bias / accumulate epilogue
+    # the convolutions of the default step, as the plan parameterised them (pointer state included), and its 64 -> 64 layers under tile 736
+    for dtype in ("bf16", "fp32"):
+        plan = graph.Plan(16, dtype, "cpu", training=True)
+        plan.define(lambda p: nets.unet_resnet(p, "resnet34", 512, 512))
+        convs = [p for p in plan._keep if isinstance(p, _lib.ConvParams) and not p.stats_slots]
+        assert len(convs) > 80
+        for i, p in enumerate(convs):
+            check(p, (dtype, i))
+            if dtype == "bf16" and p.KH == 3 and p.C0 == 64 and p.Cout == 64 and p.stride == 1 and not p.C1:
+                q = _lib.ConvParams.from_buffer_copy(p)
+                q.tile = 736
+                check(q, (dtype, i, 736))
+    assert all(seen.get(k, 0) > 0 for k in (0, 512, 640, 704, 768, 800, 1024)), seen       # per-tap, sc, scw, scn, stem, pw, halo
+    assert seen.get(736, 0) > 0, seen
+
+
 def test_bench_names_every_launch_of_the_headline_plan():
     """bench.py's instrumented pass maps every launch of the step to the kernel the library runs for it (kernel_key): a launch kind
     it does not know (a new tile id) must fail here, on CPU, not in the driver's bench run."""

@@ -1,4 +1,6 @@
-"""GPU parity tests: every C-ABI entry point against the CPU oracle (oracle/np_ops.py etc.).
+"""GPU parity tests: the C-ABI entry points against the CPU oracle (oracle/np_ops.py etc.).  The pooling / resize / element-wise /
+probability-head entry points have their op-level tests in test_ops_rest_gpu.py; tests/test_abi.py lists the compute entry points that
+no test file names, and that list is an explicit allow-list.
 
 Parity is "vs the in-repo CPU oracle" - the reference's Keras path is not executable (see
 oracle/__init__.py).  Tolerances: fp32 mode 1e-4 relative to the output scale (exact-fp32 MFMA,
@@ -1693,6 +1695,51 @@ def test_pointwise_streaming_kernel(ops, dtype, mode, shape):
                 P3.stats_partial = ops.ptr(st3)
             ops.conv2d(P3)
             np.testing.assert_allclose(host(y3), host(y), atol=tol(ref, dtype))
+
+
+@pytest.mark.parametrize("dtype", H16)
+@pytest.mark.parametrize("epilogue", ["bias"])
+@pytest.mark.parametrize("shape", [(64, 256), (256, 128)], ids=lambda s_: "%dto%d" % s_)
+def test_pointwise_shape_with_bias_and_fused_statistics_is_sized_for_the_kernel_it_runs(ops, dtype, epilogue, shape):
+    """A 1x1 convolution of a served shape with a bias AND fused statistics: the pointwise kernel has no such epilogue,
+    the per-tap kernel runs and writes ceil(P / tile pixels) columns - the sizing query, asked before the table exists, must have
+    answered for it (tests/test_host.py::test_stats_sizing_query_does_not_depend_on_the_table_pointer is the host half).  The table is
+    allocated for the larger of the two answers plus a NaN tail, so the launch cannot leave its allocation whatever the query said;
+    the written part must be [2][Cout][stats_tiles] sums of the stored output (float64) and everything behind it still NaN."""
+    from segmentation_training_pipeline_amd import _lib
+    lib = _lib.load()
+    cin, cout = shape
+    n, h, w = 2, 96, 176
+    P_ = n * h * w
+    rng = np.random.RandomState(11 + cin + cout)
+    x = q(rng.randn(n, h, w, cin), dtype)
+    wt = q(rng.randn(1, 1, cin, cout) / np.sqrt(cin), dtype)
+    _, fwd, _, _ = prep_weights(ops, wt, dtype)
+    bias_np = (rng.randn(cout) * 0.5).astype(np.float32) if epilogue == "bias" else None
+    prev_np = q(rng.randn(n, h, w, cout), dtype) if epilogue == "accumulate" else None
+    bias = keep(torch.from_numpy(bias_np).to(DEV)) if bias_np is not None else None
+    y = dev(prev_np, dtype) if prev_np is not None else keep(torch.full((n, h, w, cout), float("nan"), dtype=TD[dtype], device=DEV))
+    P = ops.conv_params(dev(x, dtype), fwd, y, N=n, Hs0=h, Ws0=w, Hv=h, Wv=w, C0=cin, KH=1, KW=1, stride=1, pad=0, Ho=h, Wo=w, Cout=cout,
+                        dtype=ops.dt(y), bias=bias, accumulate0=int(prev_np is not None))
+    before = ops.conv2d_stats_floats(P)                      # as graph.Plan.conv asks: the table does not exist yet
+    P.stats_partial = 16
+    after = ops.conv2d_stats_floats(P)
+    tail = 4096
+    st = keep(torch.full((max(before, after) + tail,), float("nan"), dtype=torch.float32, device=DEV))
+    P.stats_partial = ops.ptr(st)
+    assert not lib.stp_conv2d_pw_eligible(ops.C.byref(P)) and lib.stp_conv2d_tile_for(ops.C.byref(P)) != 800
+    ops.conv2d(P)
+    cols = P.stats_tiles
+    assert before == after == 2 * cout * cols, (before, after, cols)
+    got = host(y).astype(np.float64)
+    ref = (x.reshape(P_, cin).astype(np.float64) @ wt.reshape(cin, cout).astype(np.float64)).reshape(n, h, w, cout)
+    ref = ref + (bias_np if bias_np is not None else prev_np)
+    np.testing.assert_allclose(got, ref, atol=tol(ref, dtype))
+    table = host(st)
+    assert np.isnan(table[2 * cout * cols:]).all() and np.isfinite(table[:2 * cout * cols]).all()
+    sums = table[:2 * cout * cols].reshape(2, cout, cols).astype(np.float64).sum(-1)
+    np.testing.assert_allclose(sums[0], got.reshape(P_, cout).sum(0), rtol=1e-4, atol=2e-4 * np.abs(got).sum(axis=(0, 1, 2)).max())
+    np.testing.assert_allclose(sums[1], (got ** 2).reshape(P_, cout).sum(0), rtol=1e-4)
 
 
 @pytest.mark.parametrize("dtype", H16)

@@ -1,0 +1,788 @@
+"""GPU parity tests of the entry points that only whole-step tests used to reach: the pooling / resize / element-wise kernels of
+bn_pool.hip, the spatial dropout, the softmax activation and the loss on class probabilities of deeplab.hip, the batched
+class-collapsed weight copy.  Each C-ABI entry point is called directly and compared with a plain float64 numpy (or torch-CPU float64
+autograd) restatement of the same operation, never with a second run of a kernel.
+
+Conventions as in test_ops_gpu.py: inputs are rounded through the storage dtype first (``q``), device temporaries stay alive until the
+test ends, ``dtype`` runs over fp32 / bf16 / fp16 with the fp16 cases routed to libstp_hip_f16.so.  Every group has a case larger than
+the grid cap of its launcher (524 288 threads in bn_pool.hip, 4 194 304 in deeplab.hip) so that the grid-stride loop takes a second
+trip, a case with ragged extents (odd N, H != W, C % 8 == 4), and outputs are pre-filled with NaN so that an element nobody wrote shows.
+Bit-equality needs no tolerance; everywhere else the bound is the one the sibling test of the same family uses (``tol``: one output
+rounding plus fp32 accumulation).  Refusals are checked on the return code; a refused call launches nothing.
+"""
+import struct
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from oracle import deeplab as odeeplab  # noqa: E402
+from oracle import losses as olosses  # noqa: E402
+
+DEV = "cuda"
+TD = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+DTYPES = ["fp32", "bf16", "fp16"]
+BADARG = -1
+CAP_POOL = 2048 * 256        # grid_for (bn_pool.hip): work items one trip of the capped grid covers
+CAP_DL = 16384 * 256         # dl_grid (deeplab.hip)
+
+
+@pytest.fixture(scope="module")
+def ops():
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    from segmentation_training_pipeline_amd import ops as o
+    return o
+
+
+@pytest.fixture(autouse=True)
+def _storage_build(request):
+    """Tests parametrized with dtype "fp16" call into libstp_hip_f16.so (IEEE-half storage)."""
+    from segmentation_training_pipeline_amd import _lib
+    dt = request.node.callspec.params.get("dtype") if hasattr(request.node, "callspec") else None
+    with _lib.storage("fp16" if dt == "fp16" else "bf16"):
+        yield
+
+
+def q(a, dtype):
+    """Round a numpy array through the storage dtype (so reference and kernel see equal inputs)."""
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(TD[dtype]).to(torch.float32).numpy()
+
+
+_KEEP = []
+
+
+def keep(t):
+    _KEEP.append(t)
+    return t
+
+
+def dev(a, dtype):
+    """Device copy in the storage dtype, parked until the test ends (the C-ABI holds raw pointers only)."""
+    return keep(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(TD[dtype]).to(DEV).contiguous())
+
+
+def nans(shape, dtype):
+    return keep(torch.full(shape, float("nan"), dtype=TD[dtype], device=DEV))
+
+
+def f32(a):
+    return keep(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV))
+
+
+@pytest.fixture(autouse=True)
+def _release_device_temporaries():
+    yield
+    torch.cuda.synchronize()
+    del _KEEP[:]
+
+
+def host(t):
+    torch.cuda.synchronize()
+    return t.detach().to(torch.float32).cpu().numpy()
+
+
+def tol(ref, dtype, k=1.0):
+    s = float(np.abs(ref).max()) + 1e-6
+    # one output rounding: 2^-8 relative for bf16, 2^-11 for IEEE half (the bound is stated on the tensor's scale)
+    return {"fp32": 2e-4, "bf16": 1.2e-2, "fp16": 2e-3}[dtype] * s * k
+
+
+def rc(name, *args):
+    """Return code of a C-ABI call (refusal checks: nothing may be launched, so nothing is synchronised or read afterwards)."""
+    from segmentation_training_pipeline_amd import _lib
+    return int(getattr(_lib.load(), name)(*args))
+
+
+def bits_equal(got, want):
+    """Equal as numbers with no NaN anywhere (+0 and -0 are the same value: the kernels write a plain 0 where they mask)."""
+    return not np.isnan(got).any() and np.array_equal(got, np.asarray(want, dtype=got.dtype))
+
+
+def tie_input(rng, shape):
+    """Integers 0..3: exact in every storage dtype, and most pooling windows hold their maximum more than once."""
+    return rng.randint(0, 4, size=shape).astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# stp_maxpool2x2 / stp_maxpool2x2_bwd
+
+def pool_windows(x, k):
+    """[N,H,W,C] -> [N,H/k,W/k,C,k*k], window positions in row-major order (position = kh * k + kw)."""
+    n, h, w, c = x.shape
+    return x.reshape(n, h // k, k, w // k, k, c).transpose(0, 1, 3, 5, 2, 4).reshape(n, h // k, w // k, c, k * k)
+
+
+def pool_reference(x, k):
+    win = pool_windows(x, k)
+    idx = win.argmax(-1)                                   # numpy returns the FIRST maximum: the rule of include/stp_hip.h
+    return np.take_along_axis(win, idx[..., None], -1)[..., 0], idx
+
+
+def pool_grad_reference(idx, dy, k):
+    n, ho, wo, c = idx.shape
+    g = np.zeros((n, ho, wo, c, k * k), np.float32)           # (a routed copy: no arithmetic)
+    np.put_along_axis(g, idx[..., None], dy.astype(np.float32)[..., None], -1)
+    return g.reshape(n, ho, wo, c, k, k).transpose(0, 1, 4, 2, 5, 3).reshape(n, ho * k, wo * k, c)
+
+
+POOL2_CASES = [
+    # N, H, W, C, input: C = 4 the 4-wide fp32 / 16-bit path, 12 the 4-wide 16-bit fallback (C % 8 == 4), 64 the 8-wide 16-bit path
+    (3, 10, 6, 4, "ties"), (1, 6, 14, 12, "ties"), (2, 8, 8, 64, "ties"), (3, 6, 10, 12, "relu"), (1, 4, 4, 64, "relu"), (2, 2, 2, 4, "relu"),
+    (4, 512, 512, 64, "ties"),
+]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", POOL2_CASES, ids=lambda c: "%dx%dx%dx%d-%s" % c)
+def test_maxpool2x2_first_maximum_and_gradient_routing(ops, dtype, case):
+    """stp_maxpool2x2 / stp_maxpool2x2_bwd against numpy's argmax over the 2x2 window in row-major order.  y and idx are bit-equal to the
+    reference - on integer inputs where most windows tie (pools sit behind ReLUs on 16-bit tensors: ties are the normal case) the index
+    must be the FIRST maximum - with and without the index output; dx is bit-equal with accumulate = 0 (NaN pre-fill: every element is
+    written) and within one output rounding of dx + g with accumulate = 1, exactly unchanged where no gradient arrives."""
+    n, h, w, c, kind = case
+    rng = np.random.RandomState(100 + h + c)
+    x = tie_input(rng, (n, h, w, c)) if kind == "ties" else q(np.maximum(rng.randn(n, h, w, c), 0), dtype)
+    yref, iref = pool_reference(x, 2)
+    if kind == "ties" and x.size < 1 << 20:
+        srt = np.sort(pool_windows(x, 2), -1)
+        assert (srt[..., -1] == srt[..., -2]).mean() > 0.3                 # the maximum is held more than once in many windows
+    xd = dev(x, dtype)
+    y, idx = nans((n, h // 2, w // 2, c), dtype), keep(torch.full((n, h // 2, w // 2, c), 255, dtype=torch.uint8, device=DEV))
+    ops.maxpool2x2(xd, y, idx, n, h, w, c)
+    assert bits_equal(host(y), yref)
+    assert np.array_equal(idx.cpu().numpy(), iref.astype(np.uint8))
+    y2 = nans((n, h // 2, w // 2, c), dtype)
+    ops.maxpool2x2(xd, y2, None, n, h, w, c)                 # idx = NULL: inference
+    assert bits_equal(host(y2), yref)
+    dy = q(rng.randn(n, h // 2, w // 2, c), dtype)
+    gref = pool_grad_reference(iref, dy, 2)
+    dyd = dev(dy, dtype)
+    dx = nans((n, h, w, c), dtype)
+    ops.maxpool2x2_bwd(idx, dyd, dx, n, h, w, c, accumulate=0)
+    assert bits_equal(host(dx), gref)
+    prev = q(rng.randn(n, h, w, c), dtype)
+    dx1 = dev(prev, dtype)
+    ops.maxpool2x2_bwd(idx, dyd, dx1, n, h, w, c, accumulate=1)
+    got = host(dx1)
+    want = prev.astype(np.float64) + gref
+    np.testing.assert_allclose(got, want, atol=tol(want, dtype))
+    assert np.array_equal(got[gref == 0], prev[gref == 0])
+
+
+def test_maxpool2x2_refusals(ops):
+    """Odd H or W, C % 4 != 0 and more output rows than the grid's y extent (N * H / 2 > 65535) return STP_E_BADARG before any launch."""
+    t = keep(torch.zeros(4096, dtype=torch.float32, device=DEV))
+    i8 = keep(torch.zeros(4096, dtype=torch.uint8, device=DEV))
+    p, pi, st = ops.ptr(t), ops.ptr(i8), ops.stream()
+    for (n, h, w, c) in ((1, 5, 4, 4), (1, 4, 6 + 1, 4), (1, 4, 4, 6), (1, 4, 4, 2), (32768, 4, 2, 4), (0, 4, 4, 4)):
+        assert rc("stp_maxpool2x2", p, p, pi, n, h, w, c, ops.F32, st) == BADARG, (n, h, w, c)
+        assert rc("stp_maxpool2x2_bwd", pi, p, p, n, h, w, c, ops.F32, 0, st) == BADARG, (n, h, w, c)
+    assert rc("stp_maxpool2x2", None, p, pi, 1, 4, 4, 4, ops.F32, st) == BADARG
+    assert rc("stp_maxpool2x2_bwd", None, p, p, 1, 4, 4, 4, ops.F32, 0, st) == BADARG      # the gradient needs the index
+    assert rc("stp_maxpool2x2", p, p, pi, 1, 4, 4, 4, 77, st) == BADARG                      # not a dtype code
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# stp_maxpool_k / stp_maxpool_k_bwd
+
+POOLK_CASES = [
+    # N, H, W, C, k, input (k = H: the whole map, PSPNet level 1; C = 512: the PSPNet feature map's width)
+    (3, 5, 7, 5, 1, "ties"), (2, 4, 6, 512, 2, "ties"), (2, 6, 9, 5, 3, "ties"), (1, 12, 18, 1, 6, "ties"), (2, 6, 6, 5, 6, "ties"),
+    (1, 4, 8, 5, 4, "ties"), (2, 6, 9, 5, 3, "randn"), (1, 12, 6, 1, 6, "randn"), (3, 4, 6, 512, 2, "randn"),
+    (2, 64, 96, 512, 2, "ties"),          # 1 572 864 outputs, 6 291 456 inputs: both loops take further trips
+]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", POOLK_CASES, ids=lambda c: "%dx%dx%dx%d-k%d-%s" % c)
+def test_maxpool_k_first_maximum_and_gradient_routing(ops, dtype, case):
+    """stp_maxpool_k / stp_maxpool_k_bwd (MaxPooling2D(k, k), PSPNet `psp_pooling_type: max`) against numpy's argmax over the k x k
+    window in row-major order: y and idx bit-equal (first maximum on tied integer inputs), idx = NULL, dx bit-equal with accumulate = 0
+    and within one output rounding with accumulate = 1 (unchanged where no gradient arrives)."""
+    n, h, w, c, k, kind = case
+    rng = np.random.RandomState(200 + h + c + k)
+    x = tie_input(rng, (n, h, w, c)) if kind == "ties" else q(rng.randn(n, h, w, c), dtype)
+    yref, iref = pool_reference(x, k)
+    xd = dev(x, dtype)
+    ho, wo = h // k, w // k
+    y, idx = nans((n, ho, wo, c), dtype), keep(torch.full((n, ho, wo, c), -7, dtype=torch.int32, device=DEV))
+    ops.maxpool_k(xd, y, idx, n, h, w, c, k)
+    assert bits_equal(host(y), yref)
+    assert np.array_equal(idx.cpu().numpy(), iref.astype(np.int32))
+    y2 = nans((n, ho, wo, c), dtype)
+    ops.maxpool_k(xd, y2, None, n, h, w, c, k)
+    assert bits_equal(host(y2), yref)
+    dy = q(rng.randn(n, ho, wo, c), dtype)
+    gref = pool_grad_reference(iref, dy, k)
+    dyd = dev(dy, dtype)
+    dx = nans((n, h, w, c), dtype)
+    ops.maxpool_k_bwd(idx, dyd, dx, n, h, w, c, k, accumulate=0)
+    assert bits_equal(host(dx), gref)
+    prev = q(rng.randn(n, h, w, c), dtype)
+    dx1 = dev(prev, dtype)
+    ops.maxpool_k_bwd(idx, dyd, dx1, n, h, w, c, k, accumulate=1)
+    got = host(dx1)
+    want = prev.astype(np.float64) + gref
+    np.testing.assert_allclose(got, want, atol=tol(want, dtype))
+    assert np.array_equal(got[gref == 0], prev[gref == 0])
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_maxpool_k_window_of_minus_infinity(ops, dtype):
+    """Keras' MaxPooling2D (tf.nn.max_pool) returns -inf for a window that holds only -inf, and the finite maximum of a window that holds
+    some.  The kernel used to start its running maximum from the finite floor -3.4e38: in fp32 an all -inf window (and any window of
+    values below the floor) came back as -3.4e38 - a finite number that is not in the input - while the 16-bit builds returned -inf
+    only because the floor overflows bfloat16.  That was a bug; the running maximum now starts from the window's first element: fp32 and
+    bf16 return the window's own maximum (-inf for a window of -inf), with idx = 0 for a window of equal elements (first maximum).  The
+    IEEE-half build returns -65504 there: every 16-bit store of that build saturates at the largest finite value by design
+    (csrc/common.h), so no kernel of the build can hand an infinity on; its index is still that of the first maximum."""
+    n, h, w, c, k = 1, 4, 6, 3, 2
+    rng = np.random.RandomState(5)
+    x = q(rng.randn(n, h, w, c), dtype)
+    x[0, 0:2, 0:2, :] = -np.inf                    # a whole window
+    x[0, 2, 2, 1] = -np.inf                        # one element of a window (first position)
+    x[0, 3, 5, 2] = -np.inf                        # ... and a last position
+    if dtype == "fp32":
+        x[0, 0:2, 4:6, 0] = np.float32(-3.402e38)  # finite, below the old floor
+    yref, iref = pool_reference(x, k)
+    assert np.isneginf(yref[0, 0, 0]).all() and (iref[0, 0, 0] == 0).all()
+    y, idx = nans((n, h // k, w // k, c), dtype), keep(torch.full((n, h // k, w // k, c), -7, dtype=torch.int32, device=DEV))
+    ops.maxpool_k(dev(x, dtype), y, idx, n, h, w, c, k)
+    assert bits_equal(host(y), np.maximum(yref, np.float32(-65504.0)) if dtype == "fp16" else yref)
+    assert np.array_equal(idx.cpu().numpy(), iref.astype(np.int32))
+
+
+def test_maxpool_k_refusals(ops):
+    t = keep(torch.zeros(4096, dtype=torch.float32, device=DEV))
+    i32 = keep(torch.zeros(4096, dtype=torch.int32, device=DEV))
+    p, pi, st = ops.ptr(t), ops.ptr(i32), ops.stream()
+    for (n, h, w, c, k) in ((1, 6, 6, 4, 4), (1, 6, 4, 4, 3), (1, 6, 6, 4, 0), (1, 6, 6, 0, 2), (0, 6, 6, 4, 2), (1, 6, 6, 4, -2)):
+        assert rc("stp_maxpool_k", p, p, pi, n, h, w, c, k, ops.F32, st) == BADARG, (n, h, w, c, k)
+        assert rc("stp_maxpool_k_bwd", pi, p, p, n, h, w, c, k, ops.F32, 0, st) == BADARG, (n, h, w, c, k)
+    assert rc("stp_maxpool_k", p, None, pi, 1, 6, 6, 4, 2, ops.F32, st) == BADARG
+    assert rc("stp_maxpool_k_bwd", None, p, p, 1, 6, 6, 4, 2, ops.F32, 0, st) == BADARG
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# stp_resize_nearest / stp_resize_nearest_bwd
+
+NEAREST_CASES = [
+    # N, H, W, C, factor, ldo, coff
+    (3, 5, 7, 5, 1, 5, 0), (1, 4, 6, 4, 2, 12, 4), (2, 3, 5, 12, 4, 20, 3), (1, 3, 2, 5, 8, 9, 2), (3, 2, 3, 1, 2, 3, 2),
+    (2, 32, 48, 172, 8, 176, 4),          # 528 384 inputs (the gradient loop strides), 33.8 M outputs
+]
+SENTINEL = -7.25        # exact in every storage dtype
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", NEAREST_CASES, ids=lambda c: "%dx%dx%dx%d-f%d-ld%d+%d" % c)
+def test_resize_nearest_into_a_channel_slice_and_gradient(ops, dtype, case):
+    """stp_resize_nearest writes channels [coff, coff + C) of a [N, fH, fW, ldo] tensor: bit-equal to np.repeat there (NaN pre-fill),
+    the other columns keep their sentinel.  stp_resize_nearest_bwd reads the same slice of a gradient tensor whose other columns hold
+    unrelated values: the float64 sum of the f x f block, one output rounding, accumulate 0 (NaN pre-fill) and 1."""
+    n, h, w, c, f, ldo, coff = case
+    rng = np.random.RandomState(300 + c + f)
+    x = q(rng.randn(n, h, w, c), dtype)
+    y = keep(torch.full((n, h * f, w * f, ldo), SENTINEL, dtype=TD[dtype], device=DEV))
+    y[..., coff:coff + c] = float("nan")
+    ops.resize_nearest(dev(x, dtype), y, n, h, w, c, f, ldo, coff)
+    got = host(y)
+    assert bits_equal(got[..., coff:coff + c], np.repeat(np.repeat(x, f, axis=1), f, axis=2))
+    assert np.array_equal(got[..., :coff], np.full_like(got[..., :coff], SENTINEL))
+    assert np.array_equal(got[..., coff + c:], np.full_like(got[..., coff + c:], SENTINEL))
+    del got
+    dy = q(rng.randn(n, h * f, w * f, ldo), dtype)
+    ref = dy[..., coff:coff + c].astype(np.float64).reshape(n, h, f, w, f, c).sum(axis=(2, 4))
+    dyd = dev(dy, dtype)
+    dx = nans((n, h, w, c), dtype)
+    ops.resize_nearest_bwd(dyd, dx, n, h, w, c, f, ldo, coff, accumulate=0)
+    g0 = host(dx)
+    assert not np.isnan(g0).any()
+    np.testing.assert_allclose(g0, ref, atol=tol(ref, dtype))
+    prev = q(rng.randn(n, h, w, c), dtype)
+    dx1 = dev(prev, dtype)
+    ops.resize_nearest_bwd(dyd, dx1, n, h, w, c, f, ldo, coff, accumulate=1)
+    np.testing.assert_allclose(host(dx1), prev + ref, atol=tol(prev + ref, dtype))
+    if f == 1:
+        assert bits_equal(g0, dy[..., coff:coff + c])           # one term: a copy
+
+
+def test_resize_nearest_refusals(ops):
+    t = keep(torch.zeros(4096, dtype=torch.float32, device=DEV))
+    p, st = ops.ptr(t), ops.stream()
+    for (n, h, w, c, f, ldo, coff) in ((1, 4, 4, 4, 0, 4, 0), (1, 4, 4, 4, 2, 7, 4), (1, 4, 4, 4, 2, 8, -1), (1, 4, 4, 0, 2, 8, 0), (1, 0, 4, 4, 2, 8, 0)):
+        assert rc("stp_resize_nearest", p, p, n, h, w, c, f, ldo, coff, ops.F32, st) == BADARG
+        assert rc("stp_resize_nearest_bwd", p, p, n, h, w, c, f, ldo, coff, ops.F32, 0, st) == BADARG
+    assert rc("stp_resize_nearest", None, p, 1, 4, 4, 4, 2, 4, 0, ops.F32, st) == BADARG
+    assert rc("stp_resize_nearest_bwd", p, None, 1, 4, 4, 4, 2, 4, 0, ops.F32, 0, st) == BADARG
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# stp_relu_bwd, stp_add_inplace, stp_zero_bytes, stp_channel_sum
+
+ABOVE_CAP = 4 * (CAP_POOL + 3)        # elements: the 4-wide loops take a second trip for the first three vectors only
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("count", [4, 1028, ABOVE_CAP])
+def test_relu_mask_and_inplace_add_are_bit_exact(ops, dtype, count):
+    """stp_relu_bwd: dy <- dy * [y > 0] in place, bit-equal to numpy; y = +0 and y = -0 both mask, as does every negative y.
+    stp_add_inplace: dst <- dst + src, the fp32 sum rounded once to the storage dtype (numpy's float32 sum through torch's cast)."""
+    rng = np.random.RandomState(count % 1000)
+    y = q(rng.randn(count), dtype)
+    y[0::7] = 0.0
+    y[3::11] = -0.0
+    y[1] = np.float32(np.finfo(np.float32).tiny) if dtype != "fp16" else np.float32(2.0 ** -24)     # the smallest positive values pass
+    dy = q(rng.randn(count), dtype)
+    dyd = dev(dy, dtype)
+    ops.relu_bwd(dev(y, dtype), dyd, count)
+    assert bits_equal(host(dyd), np.where(y > 0, dy, np.float32(0)))
+    a, b = q(rng.randn(count) * 3, dtype), q(rng.randn(count), dtype)
+    ad = dev(a, dtype)
+    ops.add_inplace(ad, dev(b, dtype), count)
+    assert bits_equal(host(ad), q(a.astype(np.float32) + b.astype(np.float32), dtype))
+
+
+@pytest.mark.parametrize("nbytes", [16, 4112, 16 * (CAP_POOL + 5)])
+def test_zero_bytes_writes_exactly_its_range(ops, nbytes):
+    """stp_zero_bytes zeroes [p, p + bytes) and nothing around it (32 guard bytes on either side keep their 0xA5)."""
+    buf = keep(torch.full((nbytes + 64,), 0xA5, dtype=torch.uint8, device=DEV))
+    assert buf.data_ptr() % 16 == 0
+    ops.zero_bytes(buf[32:], nbytes)
+    torch.cuda.synchronize()
+    got = buf.cpu().numpy()
+    assert (got[:32] == 0xA5).all() and (got[32 + nbytes:] == 0xA5).all() and not got[32:32 + nbytes].any()
+
+
+def test_elementwise_refusals(ops):
+    """count % 4 != 0 (the loops are 4-wide), empty ranges, NULL and - for stp_zero_bytes - a pointer or size off the 16-byte grid."""
+    t = keep(torch.zeros(4096, dtype=torch.float32, device=DEV))
+    p, st = ops.ptr(t), ops.stream()
+    assert p % 16 == 0
+    for count in (0, 3, 6, 1023, -4):
+        assert rc("stp_relu_bwd", p, p, count, ops.F32, st) == BADARG
+        assert rc("stp_add_inplace", p, p, count, ops.F32, st) == BADARG
+    assert rc("stp_relu_bwd", None, p, 8, ops.F32, st) == BADARG and rc("stp_add_inplace", p, None, 8, ops.F32, st) == BADARG
+    assert rc("stp_relu_bwd", p, p, 8, 77, st) == BADARG and rc("stp_add_inplace", p, p, 8, 77, st) == BADARG
+    assert rc("stp_zero_bytes", p + 8, 16, st) == BADARG          # misaligned pointer
+    assert rc("stp_zero_bytes", p + 4, 16, st) == BADARG
+    assert rc("stp_zero_bytes", p, 24, st) == BADARG              # size not a multiple of 16
+    assert rc("stp_zero_bytes", p, 0, st) == BADARG and rc("stp_zero_bytes", None, 16, st) == BADARG
+    ws = keep(torch.zeros(ops.bn_workspace_bytes(8) // 4, dtype=torch.float32, device=DEV))
+    assert rc("stp_channel_sum", p, ops.F32, 8, 6, p, 0, ops.ptr(ws), ws.numel() * 4, st) == BADARG           # C % 4
+    assert rc("stp_channel_sum", p, ops.F32, 0, 8, p, 0, ops.ptr(ws), ws.numel() * 4, st) == BADARG
+    assert rc("stp_channel_sum", p, ops.F32, 8, 8, p, 0, ops.ptr(ws), 64, st) == -3                            # STP_E_WORKSPACE
+    assert torch.count_nonzero(t).item() == 0
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("C", [4, 8, 12, 264])
+@pytest.mark.parametrize("rows", [1, 63, 64, 4097])
+def test_channel_sum_against_float64(ops, dtype, rows, C):
+    """stp_channel_sum (bias gradients): out[c] (+)= sum over rows, against float64 column sums.  C = 4 / 12 run the 4-wide kernels,
+    8 / 264 the 8-wide 16-bit one (264 = 33 channel groups: row lanes that do not divide the workgroup); rows around the 64-row and
+    one-row-per-block edges.  Bound: the one the fused-statistics checks of test_ops_gpu.py put on a column sum of stored values
+    (rtol 1e-4, atol 2e-4 of the largest sum of magnitudes) - fp32 accumulation, the result is not rounded to the storage dtype."""
+    rng = np.random.RandomState(rows + C)
+    x = q(rng.randn(rows, C) + 0.25, dtype)
+    ref = x.astype(np.float64).sum(0)
+    atol = 2e-4 * np.abs(x).astype(np.float64).sum(0).max()
+    ws = keep(torch.empty(ops.bn_workspace_bytes(C) // 4, dtype=torch.float32, device=DEV))
+    out = keep(torch.full((C,), float("nan"), dtype=torch.float32, device=DEV))
+    xd = dev(x, dtype)
+    ops.channel_sum(xd, rows, C, out, 0, ws)
+    np.testing.assert_allclose(host(out), ref, rtol=1e-4, atol=atol)
+    prev = rng.randn(C).astype(np.float32) * 10
+    out1 = f32(prev)
+    ops.channel_sum(xd, rows, C, out1, 1, ws)
+    np.testing.assert_allclose(host(out1), ref + prev, rtol=1e-4, atol=atol)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("C,kind", [(4, "integers"), (8, "randn"), (12, "integers")])
+def test_channel_sum_full_size(ops, dtype, C, kind):
+    """16 x 512 x 512 rows (the headline batch: 1024 blocks of 4096 rows).  On integers in -3..3 every partial sum is an integer below
+    2^24, exact in fp32 in any order: the result must EQUAL the float64 sum, with and without accumulation onto integers - a row
+    dropped or counted twice by the block partition shows as a difference of at least 1.  On random inputs the bound of the small
+    cases holds (measured against it, not widened)."""
+    rows = 16 * 512 * 512
+    rng = np.random.RandomState(C)
+    if kind == "integers":
+        x = rng.randint(-3, 4, size=(rows, C)).astype(np.float32)
+    else:
+        x = q(np.random.default_rng(C).standard_normal((rows, C), dtype=np.float32) + np.float32(0.25), dtype)
+    ref = x.sum(0, dtype=np.float64)
+    ws = keep(torch.empty(ops.bn_workspace_bytes(C) // 4, dtype=torch.float32, device=DEV))
+    out = keep(torch.full((C,), float("nan"), dtype=torch.float32, device=DEV))
+    xd = dev(x, dtype)
+    ops.channel_sum(xd, rows, C, out, 0, ws)
+    prev = rng.randint(-50, 50, size=C).astype(np.float32)
+    out1 = f32(prev)
+    ops.channel_sum(xd, rows, C, out1, 1, ws)
+    if kind == "integers":
+        assert np.array_equal(host(out).astype(np.float64), ref) and np.array_equal(host(out1).astype(np.float64), ref + prev)
+    else:
+        atol = 2e-4 * np.abs(x).sum(0, dtype=np.float64).max()
+        np.testing.assert_allclose(host(out), ref, rtol=1e-4, atol=atol)
+        np.testing.assert_allclose(host(out1), ref + prev, rtol=1e-4, atol=atol)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# stp_bn_inference
+
+def within_column_tol(got, ref, dtype):
+    """tol() per channel: every channel is held to one output rounding on ITS scale (the zero-variance channel is 30 x the others)."""
+    bound = np.array([tol(ref[:, c], dtype) for c in range(ref.shape[1])])
+    err = np.abs(got.astype(np.float64) - ref)
+    assert not np.isnan(got).any() and (err <= bound).all(), (err.max(0) / bound).max()
+
+
+def bn_inference_reference(x, mm, mv, eps, gamma, beta, relu):
+    y = (x.astype(np.float64) - mm.astype(np.float64)) / np.sqrt(mv.astype(np.float64) + np.float64(np.float32(eps)))
+    if gamma is not None:
+        y = y * gamma.astype(np.float64)
+    if beta is not None:
+        y = y + beta.astype(np.float64)
+    return np.maximum(y, 0) if relu else y
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("case", [(1, 4, "gb"), (63, 12, "g"), (4097, 64, "b"), (255, 264, ""), (16385, 132, "gb")],
+                         ids=lambda c: "%dx%d-%s" % c)
+def test_bn_inference_from_moving_statistics(ops, dtype, case, relu):
+    """stp_bn_inference, tensor form (Cy == C, input and output in the storage dtype): y = (x - moving_mean) / sqrt(moving_var + eps) *
+    gamma + beta (+ ReLU) in float64 from the moving statistics, bound of the stp_bn_apply tests (one output rounding on the tensor's
+    scale).  gamma and / or beta NULL (scale=False / center=False); one channel with moving_var = 0 (rstd = 1 / sqrt(eps));
+    16385 x 132: 540 705 four-channel vectors, above the grid cap, on the C % 8 == 4 path."""
+    rows, Cn, affine = case
+    rng = np.random.RandomState(rows + Cn)
+    x = q(rng.randn(rows, Cn) * 2 + 0.5, dtype)
+    mm = (rng.randn(Cn) * 0.5).astype(np.float32)
+    mv = (rng.rand(Cn) * 2 + 0.1).astype(np.float32)
+    mv[1] = 0.0
+    x[:, 1] = q(mm[1] + rng.randn(rows) * 0.05, dtype)       # (keeps that channel on the scale of the others: rstd = 31.6)
+    gamma = (rng.rand(Cn) + 0.5).astype(np.float32) if "g" in affine else None
+    beta = (rng.randn(Cn) * 0.3).astype(np.float32) if "b" in affine else None
+    ref = bn_inference_reference(x, mm, mv, 1e-3, gamma, beta, relu)
+    y = nans((rows, Cn), dtype)
+    ops.bn_inference(dev(x, dtype), y, rows, Cn, Cn, f32(mm), f32(mv), 1e-3, None if gamma is None else f32(gamma),
+                     None if beta is None else f32(beta), relu)
+    within_column_tol(host(y), ref, dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("case", [(126, 1, 4), (126, 3, 4), (77, 4, 4), (126, 5, 8), (77, 3, 8), (63, 4, 8), (CAP_POOL + 77, 3, 4)],
+                         ids=lambda c: "%dx%dto%d" % c)
+def test_bn_inference_uint8_image_into_padded_channels(ops, dtype, case, relu):
+    """stp_bn_inference, image form: uint8 [rows][C] -> storage dtype [rows][Cy], Cy = 4 or 8, the padding channels hold pad_value exactly
+    (also under ReLU: the padding is a constant, not an activation) - the first layer of predict().  One case above the grid cap."""
+    rows, Cn, Cy = case
+    rng = np.random.RandomState(rows % 1000 + Cn + Cy)
+    x = rng.randint(0, 256, size=(rows, Cn)).astype(np.uint8)
+    mm = (rng.rand(Cn) * 100 + 80).astype(np.float32)
+    mv = (rng.rand(Cn) * 3000 + 500).astype(np.float32)
+    if Cn > 1:
+        mv[1] = 0.0
+        x[:, 1] = np.clip(np.rint(mm[1] + rng.randn(rows)), 0, 255).astype(np.uint8)
+    gamma = (rng.rand(Cn) + 0.5).astype(np.float32) if Cn != 3 else None
+    beta = (rng.randn(Cn) * 0.3).astype(np.float32)
+    pad = -1.5
+    ref = np.full((rows, Cy), pad, np.float64)
+    ref[:, :Cn] = bn_inference_reference(x, mm, mv, 1e-3, gamma, beta, relu)
+    y = nans((rows, Cy), dtype)
+    ops.bn_inference(keep(torch.from_numpy(x).to(DEV)), y, rows, Cn, Cy, f32(mm), f32(mv), 1e-3, None if gamma is None else f32(gamma),
+                     f32(beta), relu, pad_value=pad)
+    got = host(y)
+    within_column_tol(got[:, :Cn], ref[:, :Cn], dtype)
+    assert np.array_equal(got[:, Cn:], ref[:, Cn:])
+
+
+def test_bn_inference_refusals(ops):
+    t = keep(torch.zeros(4096, dtype=torch.float32, device=DEV))
+    u8 = keep(torch.zeros(4096, dtype=torch.uint8, device=DEV))
+    p, pu, st = ops.ptr(t), ops.ptr(u8), ops.stream()
+    call = lambda *a: rc("stp_bn_inference", *a)
+    assert call(p, ops.F32, p, ops.F32, 8, 8, 8, p, None, 1e-3, None, None, 0, 0.0, st) == BADARG        # no moving variance
+    assert call(p, ops.F32, p, ops.F32, 8, 8, 8, None, p, 1e-3, None, None, 0, 0.0, st) == BADARG        # no moving mean
+    assert call(p, ops.F32, p, ops.F32, 8, 6, 6, p, p, 1e-3, None, None, 0, 0.0, st) == BADARG           # C % 4
+    assert call(p, ops.F32, p, ops.F32, 8, 8, 12, p, p, 1e-3, None, None, 0, 0.0, st) == BADARG          # Cy != C off the image form
+    assert call(p, ops.F32, p, ops.BF16, 8, 8, 8, p, p, 1e-3, None, None, 0, 0.0, st) == BADARG          # mixed dtypes
+    assert call(pu, ops.U8, p, ops.F32, 8, 3, 6, p, p, 1e-3, None, None, 0, 0.0, st) == BADARG           # Cy not 4 / 8
+    assert call(pu, ops.U8, p, ops.F32, 8, 5, 4, p, p, 1e-3, None, None, 0, 0.0, st) == BADARG           # C > Cy
+    assert call(p, ops.F32, p, ops.F32, 0, 8, 8, p, p, 1e-3, None, None, 0, 0.0, st) == BADARG
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# stp_dropout_spatial
+
+def kept_value_rtol(dtype):
+    # y = x * fl(1 / (1 - rate)) in fp32 (two fp32 roundings: 2^-23), then one rounding to the storage dtype (half an ulp of a
+    # significand of 1: 2^-8 for bfloat16, 2^-11 for IEEE half)
+    return {"fp32": 2.0 ** -22, "bf16": 2.0 ** -8 + 2.0 ** -22, "fp16": 2.0 ** -11 + 2.0 ** -22}[dtype]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape", [(3, 35, 5), (2, 64, 12), (1, 7, 1)], ids=lambda s_: "%dx%dx%d" % s_)
+def test_dropout_spatial_mask_is_the_oracles(ops, dtype, shape):
+    """stp_dropout_spatial on [N][HW][C]: the kept (sample, channel) maps are EXACTLY oracle.deeplab.dropout_mask(step, salt, N * C, rate)
+    indexed by n * C + c, for two values of the device step counter, two salts and rates 0 / 0.25 / 0.5; kept values are x / (1 - rate)
+    to one rounding, dropped maps are exactly 0 over the whole map, and the in-place call (x == y) gives the bits of the out-of-place one."""
+    n, hw, c = shape
+    rng = np.random.RandomState(400 + hw)
+    x = q(np.sign(rng.randn(n, hw, c)) * (np.abs(rng.randn(n, hw, c)) + 0.5), dtype)        # (no zeros: a kept element is never 0)
+    assert (x != 0).all()
+    xd = dev(x, dtype)
+    state = keep(torch.zeros(2, dtype=torch.int32, device=DEV))
+    for step in (1, 123457):
+        state[0] = step
+        for salt in (7, 0x9E3779B9):
+            for rate in (0.0, 0.25, 0.5):
+                y = nans((n, hw, c), dtype)
+                ops.dropout_spatial(xd, y, n, hw, c, rate, state, salt)
+                got = host(y)
+                mask = odeeplab.dropout_mask(step, salt, n * c, rate).reshape(n, 1, c)
+                assert not np.isnan(got).any()
+                assert np.array_equal(got != 0, np.broadcast_to(mask, got.shape)), (step, salt, rate)
+                want = x.astype(np.float64) / (1.0 - rate) * mask
+                np.testing.assert_allclose(got, want, rtol=kept_value_rtol(dtype), atol=1e-7)
+                if rate == 0.0:
+                    assert mask.all() and bits_equal(got, x)
+                z = xd.clone()
+                ops.dropout_spatial(z, z, n, hw, c, rate, state, salt)
+                assert torch.equal(z, y)
+    assert int(state[0].item()) == 123457                        # the kernel reads the counter, stp_counter_tick alone advances it
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_dropout_spatial_above_the_grid_cap(ops, dtype):
+    """2 x 16 640 x 129 = 4 293 120 elements: the grid-stride loop takes a second trip, the 64-bit split into (sample, channel) is odd."""
+    n, hw, c = 2, 128 * 130, 129
+    assert n * hw * c > CAP_DL
+    rng = np.random.RandomState(9)
+    x = q(np.sign(rng.randn(n, hw, c)) * (np.abs(rng.randn(n, hw, c)) + 0.5), dtype)
+    state = keep(torch.tensor([5, 0], dtype=torch.int32, device=DEV))
+    y = nans((n, hw, c), dtype)
+    ops.dropout_spatial(dev(x, dtype), y, n, hw, c, 0.25, state, 0x51ED27)
+    got = host(y)
+    mask = odeeplab.dropout_mask(5, 0x51ED27, n * c, 0.25).reshape(n, 1, c)
+    assert 0.1 < 1 - mask.mean() < 0.45
+    assert not np.isnan(got).any() and np.array_equal(got != 0, np.broadcast_to(mask, got.shape))
+    np.testing.assert_allclose(got, x.astype(np.float64) / 0.75 * mask, rtol=kept_value_rtol(dtype), atol=1e-7)
+
+
+def test_dropout_spatial_refusals(ops):
+    t = keep(torch.zeros(4096, dtype=torch.float32, device=DEV))
+    s = keep(torch.zeros(2, dtype=torch.int32, device=DEV))
+    p, ps, st = ops.ptr(t), ops.ptr(s), ops.stream()
+    call = lambda *a: rc("stp_dropout_spatial", *a)
+    assert call(p, p, 2, 8, 4, 1.0, ps, 7, ops.F32, st) == BADARG             # rate = 1 drops everything and scales by infinity
+    assert call(p, p, 2, 8, 4, -0.1, ps, 7, ops.F32, st) == BADARG
+    assert call(p, p, 2, 8, 4, 0.5, None, 7, ops.F32, st) == BADARG
+    assert call(p, p, 0, 8, 4, 0.5, ps, 7, ops.F32, st) == BADARG and call(p, p, 2, 0, 4, 0.5, ps, 7, ops.F32, st) == BADARG
+    assert call(p, p, 2, 8, 0, 0.5, ps, 7, ops.F32, st) == BADARG and call(None, p, 2, 8, 4, 0.5, ps, 7, ops.F32, st) == BADARG
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# stp_softmax_act / stp_softmax_act_bwd
+
+SOFTMAX_CASES = [
+    # rows, classes, ldz, ldp, ldg
+    (1, 2, 2, 2, 2), (255, 2, 8, 4, 8), (255, 3, 3, 3, 3), (255, 3, 8, 5, 4), (255, 21, 21, 21, 21), (255, 21, 24, 24, 32), (255, 32, 32, 32, 32),
+    (255, 32, 40, 33, 40), (1, 21, 24, 21, 24),
+    (4200000, 3, 4, 3, 4),              # above the grid cap (one thread per row)
+]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", SOFTMAX_CASES, ids=lambda c: "%dx%d-ld%d-%d-%d" % c)
+def test_softmax_activation_and_gradient(ops, dtype, case):
+    """stp_softmax_act on the first `classes` columns of [rows][ldz] logits into [rows][ldp] probabilities (padding columns of p keep
+    their sentinel) against a float64 softmax, bound of the sigmoid-activation check of test_ops_gpu.py (1e-6 fp32, 4e-3 16-bit);
+    rows with logits +-80 (+-6e4 in fp16) give no NaN and every row sums to 1 within one storage rounding (each stored class is
+    p_c (1 + d), |d| <= 2^-8 bf16 / 2^-11 fp16 / 2^-23 fp32, and sum p_c = 1) plus 1e-7 of fp32 arithmetic per class.  stp_softmax_act_bwd: dz_c = p_c (dp_c - sum_k p_k dp_k)
+    evaluated in float64 on the kernel's own stored p, bound of the sigmoid-gradient check (half of tol on dp's scale); the padding
+    columns of dz are written 0; dp == dz in place gives the same bits."""
+    rows, classes, ldz, ldp, ldg = case
+    rng = np.random.RandomState(500 + classes + ldz)
+    z = q(rng.randn(rows, ldz) * 3, dtype)
+    big = 6e4 if dtype == "fp16" else 80.0
+    z[0, :classes] = q(np.array([big] + [-big] * (classes - 1)), dtype)
+    z[rows // 2, :classes] = q(np.array([-big] * (classes - 1) + [big]), dtype)
+    z[rows - 1, :classes] = q(np.full(classes, -big), dtype)
+    if rows > 3:
+        z[1, :classes] = q(np.full(classes, big), dtype)
+    p = keep(torch.full((rows, ldp), SENTINEL, dtype=TD[dtype], device=DEV))
+    p[:, :classes] = float("nan")
+    ops.softmax_act(dev(z, dtype), p, rows, classes, ldz, ldp)
+    got = host(p)
+    z64 = z[:, :classes].astype(np.float64)
+    e = np.exp(z64 - z64.max(-1, keepdims=True))
+    pref = e / e.sum(-1, keepdims=True)
+    assert not np.isnan(got).any()
+    np.testing.assert_allclose(got[:, :classes], pref, atol=1e-6 if dtype == "fp32" else 4e-3)
+    assert np.array_equal(got[:, classes:], np.full_like(got[:, classes:], SENTINEL))
+    ulp = {"fp32": 2.0 ** -23, "bf16": 2.0 ** -8, "fp16": 2.0 ** -11}[dtype]
+    assert np.abs(got[:, :classes].astype(np.float64).sum(-1) - 1.0).max() <= ulp + classes * 1e-7
+    # gradient, on the stored probabilities
+    dp = q(rng.randn(rows, ldg), dtype)
+    ps = got[:, :classes].astype(np.float64)
+    d64 = dp[:, :classes].astype(np.float64)
+    dref = ps * (d64 - (ps * d64).sum(-1, keepdims=True))
+    dpd = dev(dp, dtype)
+    dz = nans((rows, ldg), dtype)
+    ops.softmax_act_bwd(p, dpd, dz, rows, classes, ldp, ldg)
+    gz = host(dz)
+    assert not np.isnan(gz).any()
+    np.testing.assert_allclose(gz[:, :classes], dref, atol=tol(dp, dtype, 0.5))
+    assert np.array_equal(gz[:, classes:], np.zeros_like(gz[:, classes:]))
+    inplace = dpd.clone()
+    ops.softmax_act_bwd(p, inplace, inplace, rows, classes, ldp, ldg)
+    assert torch.equal(inplace, dz)
+
+
+def test_softmax_activation_refusals(ops):
+    t = keep(torch.zeros(4096, dtype=torch.float32, device=DEV))
+    p, st = ops.ptr(t), ops.stream()
+    for (rows, classes, lda, ldb) in ((8, 1, 4, 4), (8, 33, 40, 40), (8, 3, 2, 4), (8, 3, 4, 2), (0, 3, 4, 4)):
+        assert rc("stp_softmax_act", p, p, rows, classes, lda, ldb, ops.F32, st) == BADARG
+        assert rc("stp_softmax_act_bwd", p, p, p, rows, classes, lda, ldb, ops.F32, st) == BADARG
+    assert rc("stp_softmax_act", None, p, 8, 3, 4, 4, ops.F32, st) == BADARG
+    assert rc("stp_softmax_act_bwd", p, None, p, 8, 3, 4, 4, ops.F32, st) == BADARG
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# stp_prob_cce_dice
+
+CCE_CASES = [
+    # pixels, classes, ldc, dl_channels
+    (1, 2, 2, 2), (1, 3, 4, 8), (511, 2, 2, 8), (511, 3, 8, 4), (511, 21, 24, 24), (511, 21, 21, 32),
+    (16 * 512 * 512, 2, 2, 8),                   # the headline batch
+    (16 * 512 * 512 + 511, 3, 4, 4),             # above the grid cap of the gradient kernel (one thread per pixel)
+]
+W_CCE, W_DICE = 1.0, 0.5
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", CCE_CASES, ids=lambda c: "%dx%d-ld%d-%d" % c)
+def test_probability_cce_dice_loss_scalars_and_gradient(ops, dtype, case):
+    """stp_prob_cce_dice against oracle/losses.py evaluated in float64 on one-hot targets: categorical_crossentropy + 0.5 * dice_loss
+    (scalars 0-2), dice at 0.5, binary accuracy, the raw sums of p, y and p y (5-7; sum y is an integer count: exact), iou_coef and
+    iot (8, 9); torch float64 autograd for the gradient.  The probabilities are uniform draws that do NOT sum to 1 (the resize in front
+    of the loss does not preserve the sum: the kernel renormalises); hand-set rows put p_target / S below 1e-7 and at 1 (the clip is
+    active: the cross-entropy gradient of the whole row is exactly 0, asserted on a run with w_dice = 0), and some targets are >=
+    classes (ignored by the one-hot sums, zero cross-entropy gradient).  Padding columns of dprobs are written 0; dprobs = NULL gives
+    the same scalars.  Bounds: those of the stp_prob_bce_dice / stp_softmax_cce_dice checks of test_ops_gpu.py (loss 2e-5 relative,
+    dice terms 1e-5, accuracy 1e-6; gradient rtol 2e-4 fp32 / 2e-2 16-bit) with an absolute floor of 1e-4 / pixels - never above the
+    sibling's 1e-6, which at 4 M pixels would exceed the gradient itself - plus half a subnormal step in fp16.  Elements on a kink
+    (rows whose p_target / S lies within fp32 rounding of a clip boundary) are the only ones excluded: fewer than 1 %."""
+    pixels, classes, ldc, dlc = case
+    rng = np.random.RandomState(600 + classes + ldc)
+    pr = q(rng.random_sample((pixels, ldc)).astype(np.float32) * 0.98 + 0.01, dtype)
+    t = rng.randint(0, classes, size=pixels).astype(np.uint8)
+    if pixels > 8:
+        t[5::97] = classes                                      # ignore label
+        t[7] = 255
+        t[0], t[1], t[2] = 0, 1, 0
+        pr[0, :classes] = q(np.array([1e-9] + [0.5] * (classes - 1)), dtype)          # p_t / S below the clip
+        pr[1, :classes] = q(np.array([0.0, 1.0] + [0.0] * (classes - 2)), dtype)      # p_t / S = 1: above the clip
+        pr[2, :classes] = q(np.array([0.75] + [0.125] * (classes - 1)), dtype)
+    P = pr[:, :classes].astype(np.float64)
+    valid = t < classes
+    onehot = np.zeros((pixels, classes), np.float64)
+    onehot[np.nonzero(valid)[0], t[valid]] = 1.0
+    pt = torch.from_numpy(P.copy()).requires_grad_(True)
+    yt = torch.from_numpy(onehot)
+    cce = olosses.categorical_crossentropy(yt, pt)
+    dice = olosses.dice_loss(yt, pt)
+    (W_CCE * cce + W_DICE * dice).backward()
+    loss = float((W_CCE * cce + W_DICE * dice).detach())
+    pd_ = pt.detach()
+    scal = keep(torch.full((10,), float("nan"), dtype=torch.float32, device=DEV))
+    dl = nans((pixels, dlc), dtype)
+    ws = keep(torch.empty(ops.loss_workspace_bytes() // 4, dtype=torch.float32, device=DEV))
+    prd, td = dev(pr, dtype), keep(torch.from_numpy(t).to(DEV))
+    ops.prob_cce_dice(prd, td, pixels, classes, ldc, W_CCE, W_DICE, scal, dl, dlc, ws)
+    s = host(scal).astype(np.float64)
+    assert abs(s[0] - loss) < 2e-5 * max(1.0, abs(loss)), (s[0], loss)
+    assert abs(s[1] - float(cce.detach())) < 2e-5 * max(1.0, abs(float(cce.detach()))), (s[1], float(cce.detach()))
+    assert abs(s[2] - float(dice.detach())) < 1e-5, (s[2], float(dice.detach()))
+    assert abs(s[3] - float(olosses.dice_metric(yt, pd_))) < 1e-5
+    assert abs(s[4] - float(olosses.binary_accuracy(yt, pd_))) < 1e-6
+    assert abs(s[5] - P.sum()) <= 2e-5 * P.sum() and s[6] == onehot.sum() and abs(s[7] - (P * onehot).sum()) <= 2e-5 * max(1.0, (P * onehot).sum())
+    assert abs(s[8] - float(olosses.iou_coef(yt, pd_))) < 1e-5 and abs(s[9] - float(olosses.iot_metric(yt, pd_))) < 1e-5
+    g = host(dl)
+    assert not np.isnan(g).any()
+    assert np.array_equal(g[:, classes:], np.zeros_like(g[:, classes:]))
+    refg = pt.grad.numpy()
+    qt = np.where(valid, P[np.arange(pixels), np.minimum(t, classes - 1)], 0.0) / P.sum(-1)
+    hi = float(np.float32(1.0) - np.float32(1e-7))
+    kink = valid & ((np.abs(qt - 1e-7) <= 1e-13) | ((qt >= hi - 1.2e-7) & (qt < 1.0)))
+    assert kink.mean() < 0.01
+    ok = ~kink
+    atol = min(1e-6, 1e-4 / pixels) + (2.0 ** -25 if dtype == "fp16" else 0.0)
+    np.testing.assert_allclose(g[ok, :classes], refg[ok], rtol=2e-4 if dtype == "fp32" else 2e-2, atol=atol)
+    # scalars only
+    scal2 = keep(torch.full((10,), float("nan"), dtype=torch.float32, device=DEV))
+    ops.prob_cce_dice(prd, td, pixels, classes, ldc, W_CCE, W_DICE, scal2, None, 0, ws)
+    assert np.array_equal(host(scal2), host(scal))
+    # the cross-entropy term alone: exactly 0 where the clip is active and where the target is ignored
+    dl2 = nans((pixels, dlc), dtype)
+    ops.prob_cce_dice(prd, td, pixels, classes, ldc, 1.0, 0.0, scal2, dl2, dlc, ws)
+    g2 = host(dl2)
+    clipped = ~valid | (qt < 1e-7 * (1 - 1e-6)) | (qt >= 1.0)
+    if pixels > 8:
+        assert clipped[0] and clipped[1] and clipped[5] and clipped[7] and not clipped[2]
+    assert not g2[clipped].any()
+    live = ~clipped & ~kink
+    assert (g2[live][:, :classes] != 0).any(axis=-1).all() or dtype == "fp16"      # (fp16 flushes the 1 / 4 M gradients of the large cases)
+
+
+def test_probability_cce_dice_refusals(ops):
+    t = keep(torch.zeros(4096, dtype=torch.float32, device=DEV))
+    u8 = keep(torch.zeros(4096, dtype=torch.uint8, device=DEV))
+    ws = keep(torch.zeros(ops.loss_workspace_bytes() // 4, dtype=torch.float32, device=DEV))
+    p, pu, pw, nb, st = ops.ptr(t), ops.ptr(u8), ops.ptr(ws), ws.numel() * 4, ops.stream()
+    call = lambda *a: rc("stp_prob_cce_dice", *a)
+    assert call(p, pu, 8, 1, 4, ops.F32, 1.0, 0.5, p, p, 4, pw, nb, st) == BADARG           # one class: stp_prob_bce_dice
+    assert call(p, pu, 8, 33, 40, ops.F32, 1.0, 0.5, p, p, 40, pw, nb, st) == BADARG
+    assert call(p, pu, 8, 3, 2, ops.F32, 1.0, 0.5, p, p, 4, pw, nb, st) == BADARG           # ldc < classes
+    assert call(p, pu, 8, 3, 4, ops.F32, 1.0, 0.5, p, p, 2, pw, nb, st) == BADARG           # dl_channels < classes
+    assert call(p, pu, 0, 3, 4, ops.F32, 1.0, 0.5, p, p, 4, pw, nb, st) == BADARG
+    assert call(p, None, 8, 3, 4, ops.F32, 1.0, 0.5, p, p, 4, pw, nb, st) == BADARG
+    assert call(p, pu, 8, 3, 4, ops.F32, 1.0, 0.5, p, p, 4, pw, 64, st) == -3               # STP_E_WORKSPACE
+    torch.cuda.synchronize()
+    assert torch.count_nonzero(t).item() == 0 and torch.count_nonzero(ws).item() == 0       # nothing ran
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# stp_weight_prepare_upcollapse_batched
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_batched_upcollapse_weight_prepare_equals_per_layer(ops, dtype):
+    """stp_weight_prepare_upcollapse_batched (one launch per step for every decoder stage, descriptor table on the device) writes exactly
+    what stp_weight_prepare_upcollapse writes layer by layer: three layers of different shapes - 16-byte vector path, element-wise path
+    (C0 % 8 != 0), Cout off the 16-row grid (zero rows behind it)."""
+    from segmentation_training_pipeline_amd import _lib
+    assert int(_lib.load().stp_weight_prepare_upcollapse_desc_bytes()) == 32
+    rng = np.random.RandomState(8)
+    layers = [(32, 128, 64), (40, 20, 12), (17, 8, 0)]                   # Cout, C0 (upsampled source), C1 (skip)
+    tab, outs = b"", []
+    for co, c0, c1 in layers:
+        master = f32(rng.randn(co, 3, 3, c0 + c1))
+        rows = (co + 15) // 16 * 16
+        one, many = nans((rows * 16 * c0,), dtype), nans((rows * 16 * c0,), dtype)
+        _lib.call("stp_weight_prepare_upcollapse", ops.ptr(master), ops.ptr(one), co, c0, c1, ops.dt(one), ops.stream())
+        tab += struct.pack("<QQiiii", ops.ptr(master), ops.ptr(many), co, rows, c0, c0 + c1)
+        outs.append((one, many))
+    desc = keep(torch.frombuffer(bytearray(tab), dtype=torch.uint8).to(DEV))
+    _lib.call("stp_weight_prepare_upcollapse_batched", desc.data_ptr(), len(layers), ops.dt(outs[0][0]), ops.stream())
+    for (co, c0, c1), (one, many) in zip(layers, outs):
+        a, b = host(one), host(many)
+        assert not np.isnan(a).any() and np.array_equal(a, b), (co, c0, c1)
+        assert not a.reshape(-1, 16 * c0)[co:].any()
+    assert rc("stp_weight_prepare_upcollapse_batched", None, 3, ops.dt(outs[0][0]), ops.stream()) == BADARG
+    assert rc("stp_weight_prepare_upcollapse_batched", desc.data_ptr(), 0, ops.dt(outs[0][0]), ops.stream()) == BADARG
