@@ -733,6 +733,38 @@ int64_t stp_calib_mfma_flops(int32_t blocks, int32_t iters);
 int stp_calib_mfma(float* out, int32_t blocks, int32_t iters, void* stream);
 int stp_calib_copy(void* dst, const void* src, int64_t bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Channel squeeze-and-excitation of the SE-ResNet basic unit (classification_models `seresnet18/34`: the gate sits on the residual
+ * branch, before the Add; reduction 16).  With u = conv2's output and sc the shortcut, both [N, HW, C] in the storage dtype:
+ *     z = mean over HW of u;  h = relu(z W1 + b1);  s = sigmoid(h W2 + b2);  x = u * s + sc        (ONE rounding, of x)
+ * W1 [C][R], b1 [R], W2 [R][C], b2 [C] are fp32 masters in the Keras Conv2D(1x1) layouts; z, s [N][C] and h [N][R] stay fp32.
+ * Served shapes: C % 8 == 0, 16 <= C <= 512, 1 <= R <= 32; anything else is STP_E_BADARG.  The tensor passes work on items =
+ * (image, one of stp_se_chunks(N, HW, C) runs of consecutive pixels); every reduction is two-stage in a fixed order (no atomics):
+ *   stp_se_squeeze    : per-item channel sums of u into the workspace ([N][chunks][C] fp32, stp_se_workspace_bytes; host-only query).
+ *   stp_se_excite     : one workgroup per image adds the chunks in a fixed order, writes z, h, s.
+ *   stp_se_scale_add  : x = u * s + sc with 16-byte accesses; stats != NULL: also the per-item sum / sum of squares of the STORED x as a
+ *                       [2][C][N * chunks] table for stp_bn_finalize (the next BatchNormalization's batch statistics).  NULL: inference.
+ * Gradient, given dx (the shortcut's gradient IS dx):
+ *   stp_se_bwd_reduce : per-item channel sums of dx * u (same workspace layout).
+ *   stp_se_excite_bwd : per image ds = the chunks in the same fixed order, da2 = ds s (1 - s) [N][C], da1 = (da2 W2^T) [h > 0] [N][R],
+ *                       dz = da1 W1^T [N][C]; then dW1 = z^T da1, db1, dW2 = h^T da2, db2 summed over the images IN IMAGE ORDER and
+ *                       WRITTEN (not accumulated).  Two launches.
+ *   stp_se_bwd_apply  : du = dx * s + dz / HW (ONE rounding). */
+int32_t stp_se_chunks(int32_t N, int64_t HW, int32_t C);
+size_t stp_se_workspace_bytes(int32_t N, int64_t HW, int32_t C);
+int stp_se_squeeze(const void* u, int32_t dtype, int32_t N, int64_t HW, int32_t C, float* workspace, size_t workspace_bytes, void* stream);
+int stp_se_excite(const float* workspace, int32_t N, int64_t HW, int32_t C, int32_t R, const float* W1, const float* b1, const float* W2,
+                  const float* b2, float* z, float* h, float* s, void* stream);
+int stp_se_scale_add(const void* u, const void* shortcut, void* x, int32_t dtype, int32_t N, int64_t HW, int32_t C, const float* s,
+                     float* stats, void* stream);
+int stp_se_bwd_reduce(const void* dx, const void* u, int32_t dtype, int32_t N, int64_t HW, int32_t C, float* workspace,
+                      size_t workspace_bytes, void* stream);
+int stp_se_excite_bwd(const float* workspace, int32_t N, int64_t HW, int32_t C, int32_t R, const float* W1, const float* W2, const float* z,
+                      const float* h, const float* s, float* da2, float* da1, float* dz, float* dW1, float* db1, float* dW2, float* db2,
+                      void* stream);
+int stp_se_bwd_apply(const void* dx, void* du, int32_t dtype, int32_t N, int64_t HW, int32_t C, const float* s, const float* dz,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -196,6 +196,14 @@ SIGNATURES = {
     "stp_calib_mfma_flops": (i64, [i32, i32]),
     "stp_calib_mfma": (i32, [vp, i32, i32, vp]),
     "stp_calib_copy": (i32, [vp, vp, i64, vp]),
+    "stp_se_chunks": (i32, [i32, i64, i32]),
+    "stp_se_workspace_bytes": (sz, [i32, i64, i32]),
+    "stp_se_squeeze": (i32, [vp, i32, i32, i64, i32, vp, sz, vp]),
+    "stp_se_excite": (i32, [vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "stp_se_scale_add": (i32, [vp, vp, vp, i32, i32, i64, i32, vp, vp, vp]),
+    "stp_se_bwd_reduce": (i32, [vp, vp, i32, i32, i64, i32, vp, sz, vp]),
+    "stp_se_excite_bwd": (i32, [vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "stp_se_bwd_apply": (i32, [vp, vp, i32, i32, i64, i32, vp, vp, vp]),
 }
 
 _libs = {}          # storage format ("bf16" | "fp16") -> loaded library

@@ -299,7 +299,10 @@ class HipSegModel(object):
         rng = np.random.RandomState(seed)
         w = OrderedDict()
         for name, info in self.plan.params.items():
-            if info.kind in ("kernel", "tkernel"):
+            if info.kind == "sekernel":         # Plan.se: Keras (1, 1, in, out) as stored; an encoder kernel (he_uniform)
+                limit = np.sqrt(6.0 / info.shape[2])
+                w[name] = rng.uniform(-limit, limit, size=info.shape).astype(np.float32)
+            elif info.kind in ("kernel", "tkernel"):
                 co, kh, kw, ci = info.shape
                 enc = any(name.startswith(pfx) for pfx in nets.ENCODER_PREFIXES)
                 limit = np.sqrt(6.0 / (kh * kw * ci)) if enc else np.sqrt(6.0 / (kh * kw * ci + kh * kw * co))

@@ -649,6 +649,11 @@ class Plan(object):
                 st, tiles = x.meta["stats_table"]
             self._emit(self.fwd, "stp_bn_finalize", st.data_ptr(), tiles, x.rows, Cn, eps, momentum, mean.data_ptr(),
                        rstd.data_ptr(), self._sptr(mm), self._sptr(mv))
+        elif x.meta.get("stats_table") is not None:
+            # a [2][C][columns] table that no convolution wrote (Plan.se: the scale-add pass sums the tensor it stores)
+            st, tiles = x.meta["stats_table"]
+            self._emit(self.fwd, "stp_bn_finalize", st.data_ptr(), tiles, x.rows, Cn, eps, momentum, mean.data_ptr(),
+                       rstd.data_ptr(), self._sptr(mm), self._sptr(mv))
         else:
             self._emit(self.fwd, "stp_bn_stats", x.buf.data_ptr(), self.cdt, x.rows, Cn, eps, momentum, mean.data_ptr(),
                        rstd.data_ptr(), self._sptr(mm), self._sptr(mv), self.ws_bn.data_ptr(), self.ws_bn.numel() * 4)
@@ -1220,6 +1225,70 @@ class Plan(object):
                 else:
                     self._emit(self.bwd, "stp_add_inplace", self._gradbuf(skip).data_ptr(), dy.data_ptr(), y.rows * out.gradC,
                                self.cdt)
+
+        self._tape.append(back)
+        return out
+
+    def se(self, name, u, shortcut, reduction=16, bn_stats=True):
+        """Channel squeeze-and-excitation on the residual branch of an SE-ResNet basic unit, with the unit's Add():
+        ``x = u * sigmoid(relu(mean_hw(u) W1 + b1) W2 + b2) + shortcut`` (csrc/se.hip; the arithmetic and its rounding points are
+        stated at stp_se_* in include/stp_hip.h).  Parameters in the Keras Conv2D(1x1, use_bias=True) layouts: ``name_fc1/kernel``
+        (1, 1, C, C / reduction), ``name_fc1/bias``, ``name_fc2/kernel`` (1, 1, C / reduction, C), ``name_fc2/bias`` - fp32 masters, read
+        as they are.  ``bn_stats``: the scale-add pass also sums the tensor it stores for the BatchNormalization that follows."""
+        if (u.H, u.W, u.C) != (shortcut.H, shortcut.W, shortcut.C) or u.gradC != u.C or shortcut.gradC != u.C:
+            raise StpShapeError("%s: cannot gate %dx%dx%d onto a %dx%dx%d shortcut" % (name, u.H, u.W, u.C, shortcut.H, shortcut.W, shortcut.C))
+        Cn, HW = u.C, u.H * u.W
+        R = Cn // int(reduction)
+        chunks = int(self.lib.stp_se_chunks(self.N, HW, Cn))
+        if chunks < 1 or not 1 <= R <= 32:
+            raise StpShapeError("%s: squeeze-and-excitation serves 16..512 channels in multiples of 8 with 1..32 hidden units (got %d / %d)"
+                                % (name, Cn, R))
+        w1 = self.param(name + "_fc1/kernel", (1, 1, Cn, R), "sekernel")
+        b1 = self.param(name + "_fc1/bias", (R,), "bias")
+        w2 = self.param(name + "_fc2/kernel", (1, 1, R, Cn), "sekernel")
+        b2 = self.param(name + "_fc2/bias", (Cn,), "bias")
+        out = self._new(name, u.H, u.W, Cn, u.needs_grad or shortcut.needs_grad or w1.trainable)
+        self._use(u, shortcut)
+        if self.dry:
+            return out
+        wsp, wsb = self._scratch(self.lib.stp_se_workspace_bytes(self.N, HW, Cn))      # [N][chunks][C] partial sums, forward and backward
+        z, s = self._alloc((self.N * Cn,), torch.float32), self._alloc((self.N * Cn,), torch.float32)
+        h = self._alloc((_rup(self.N * R, 4),), torch.float32)
+        tiles = self.N * chunks
+        st = self._alloc((2 * Cn * tiles,), torch.float32) if (bn_stats and self.training) else None
+        self._emit(self.fwd, "stp_se_squeeze", u.buf.data_ptr(), self.cdt, self.N, HW, Cn, wsp, wsb)
+        self._emit(self.fwd, "stp_se_excite", wsp, self.N, HW, Cn, R, self._pptr(w1), self._pptr(b1), self._pptr(w2), self._pptr(b2),
+                   z.data_ptr(), h.data_ptr(), s.data_ptr())
+        self._emit(self.fwd, "stp_se_scale_add", u.buf.data_ptr(), shortcut.buf.data_ptr(), out.buf.data_ptr(), self.cdt, self.N, HW, Cn,
+                   s.data_ptr(), st.data_ptr() if st is not None else None)
+        if st is not None:
+            out.meta["stats_table"] = (st, tiles)        # no meta["stats"]: Plan.bn hands the table to stp_bn_finalize as it is
+        if not self.training:
+            return out
+
+        def back():
+            if not out.needs_grad or not out.grad_ready:
+                return
+            dx = out.grad           # read three times below, never rewritten here
+            if shortcut.needs_grad:
+                if not shortcut.grad_ready:
+                    shortcut.grad, shortcut.grad_ready = dx, True      # first gradient of the shortcut: alias, later writers accumulate
+                else:
+                    self._emit(self.bwd, "stp_add_inplace", self._gradbuf(shortcut).data_ptr(), dx.data_ptr(), out.rows * Cn, self.cdt)
+            da2, dz = self._alloc((self.N * Cn,), torch.float32), self._alloc((self.N * Cn,), torch.float32)
+            da1 = self._alloc((_rup(self.N * R, 4),), torch.float32)
+            self._emit(self.bwd, "stp_se_bwd_reduce", dx.data_ptr(), u.buf.data_ptr(), self.cdt, self.N, HW, Cn, wsp, wsb)
+            # (parameter gradients are WRITTEN, summed over the images in image order; addresses asked in declaration order reversed)
+            g2b, g2, g1b, g1 = self._gptr(b2), self._gptr(w2), self._gptr(b1), self._gptr(w1)
+            self._emit(self.bwd, "stp_se_excite_bwd", wsp, self.N, HW, Cn, R, self._pptr(w1), self._pptr(w2), z.data_ptr(), h.data_ptr(),
+                       s.data_ptr(), da2.data_ptr(), da1.data_ptr(), dz.data_ptr(), g1, g1b, g2, g2b)
+            if u.needs_grad:
+                # u's gradient is conv2's dY, which a pending grouped weight gradient reads until it is issued: a buffer of its own
+                if u.grad_ready:
+                    raise StpShapeError("%s: the gated tensor must have no other consumer" % name)
+                self._emit(self.bwd, "stp_se_bwd_apply", dx.data_ptr(), self._gradbuf(u).data_ptr(), self.cdt, self.N, HW, Cn, s.data_ptr(),
+                           dz.data_ptr())
+                u.grad_ready = True
 
         self._tape.append(back)
         return out

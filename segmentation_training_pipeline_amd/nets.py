@@ -15,6 +15,10 @@ Fusions expressed here (none changes the arithmetic of the Keras graph):
 
 RESNET_UNITS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3), "resnet50": (3, 4, 6, 3), "resnet101": (3, 4, 23, 3),
                 "resnet152": (3, 8, 36, 3)}
+# classification_models `seresnet18/34`: the pre-activation basic units above with a channel squeeze-and-excitation gate (reduction 16) on
+# the residual branch of every unit, before the Add (Plan.se).  The reference does not pin that package's arithmetic; it is fixed by
+# include/stp_hip.h (stp_se_*) and restated in tests/_se_reference.py.
+SE_RESNETS = {"seresnet18": "resnet18", "seresnet34": "resnet34"}
 BOTTLENECK = ("resnet50", "resnet101", "resnet152")   # residual_bottleneck_block: 1x1 f, 3x3 f (carries the stride), 1x1 4f
 STAGE_FILTERS = (64, 128, 256, 512)
 BN_EPS_ENCODER = 2e-5
@@ -26,7 +30,7 @@ VGG_FILTERS = (64, 128, 256, 512, 512)
 
 
 def known_backbones():
-    return sorted(RESNET_UNITS) + sorted(VGG_BLOCKS) + ["mobilenetv2", "xception"]
+    return sorted(RESNET_UNITS) + sorted(SE_RESNETS) + sorted(VGG_BLOCKS) + ["mobilenetv2", "xception"]
 
 
 def _resnet_encoder(plan, backbone, H, W, in_ch, stop_stage=None):
@@ -34,6 +38,8 @@ def _resnet_encoder(plan, backbone, H, W, in_ch, stop_stage=None):
     ``stop_stage``: build only up to that stage's unit-1 relu1 (PSPNet cuts the backbone there); the first value is None."""
     if (H % 32 or W % 32) and stop_stage is None:
         raise ValueError("input height/width must be divisible by 32")
+    se = backbone in SE_RESNETS
+    backbone = SE_RESNETS.get(backbone, backbone)
     units = RESNET_UNITS[backbone]
     ex = 4 if backbone in BOTTLENECK else 1
     img = plan.input_u8("image", H, W, in_ch)
@@ -63,6 +69,12 @@ def _resnet_encoder(plan, backbone, H, W, in_ch, stop_stage=None):
                 #  depth form; stride 1, the first unit of stage 1: the centre tap of a second source on the halo kernel)
                 y = plan.conv(pre + "conv1", a, f, 3, stride=stride, pad=1, bn_stats=True, fold_shortcut=shortcut if u == 1 else None)
                 y = plan.bn(pre + "bn2", y, BN_EPS_ENCODER, relu=True)
+                if se:
+                    # (nothing normalises conv2's output and the Add follows the gate: plain launch, then squeeze / excite / scale-add,
+                    #  whose last pass also sums the stored tensor for the next unit's bn1)
+                    y = plan.conv(pre + "conv2", y, f, 3, stride=1, pad=1)
+                    x = plan.se(pre + "se", y, shortcut)
+                    continue
                 x = plan.conv(pre + "conv2", y, f, 3, stride=1, pad=1, residual=shortcut, bn_stats=True)
             else:
                 y = plan.conv(pre + "conv1", a, f, 1, bn_stats=True)

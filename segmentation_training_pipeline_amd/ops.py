@@ -228,6 +228,41 @@ def add_inplace(dst, src, count):
     _lib.call("stp_add_inplace", ptr(dst), ptr(src), count, dt(dst), stream())
 
 
+# channel squeeze-and-excitation (csrc/se.hip): W1 [C][R], b1 [R], W2 [R][C], b2 [C]; z, s, da2, dz [N][C]; h, da1 [N][R]; all fp32
+def se_chunks(N, HW, Cn):
+    return int(_lib.load().stp_se_chunks(N, HW, Cn))
+
+
+def se_workspace_bytes(N, HW, Cn):
+    return int(_lib.load().stp_se_workspace_bytes(N, HW, Cn))
+
+
+def se_squeeze(u, N, HW, Cn, workspace):
+    _lib.call("stp_se_squeeze", ptr(_dev(u)), dt(u), N, HW, Cn, ptr(workspace), workspace.numel() * workspace.element_size(), stream())
+
+
+def se_excite(workspace, N, HW, Cn, R, W1, b1, W2, b2, z, h, s):
+    _lib.call("stp_se_excite", ptr(_dev(workspace)), N, HW, Cn, R, ptr(W1), ptr(b1), ptr(W2), ptr(b2), ptr(z), ptr(h), ptr(s), stream())
+
+
+def se_scale_add(u, shortcut, x, N, HW, Cn, s, stats=None):
+    _lib.call("stp_se_scale_add", ptr(_dev(u)), ptr(shortcut), ptr(x), dt(u), N, HW, Cn, ptr(s), ptr(stats), stream())
+
+
+def se_bwd_reduce(dx, u, N, HW, Cn, workspace):
+    _lib.call("stp_se_bwd_reduce", ptr(_dev(dx)), ptr(u), dt(u), N, HW, Cn, ptr(workspace), workspace.numel() * workspace.element_size(),
+              stream())
+
+
+def se_excite_bwd(workspace, N, HW, Cn, R, W1, W2, z, h, s, da2, da1, dz, dW1, db1, dW2, db2):
+    _lib.call("stp_se_excite_bwd", ptr(_dev(workspace)), N, HW, Cn, R, ptr(W1), ptr(W2), ptr(z), ptr(h), ptr(s), ptr(da2), ptr(da1), ptr(dz),
+              ptr(dW1), ptr(db1), ptr(dW2), ptr(db2), stream())
+
+
+def se_bwd_apply(dx, du, N, HW, Cn, s, dz):
+    _lib.call("stp_se_bwd_apply", ptr(_dev(dx)), ptr(du), dt(dx), N, HW, Cn, ptr(s), ptr(dz), stream())
+
+
 def loss_workspace_bytes():
     return int(_lib.load().stp_loss_workspace_bytes())
 
