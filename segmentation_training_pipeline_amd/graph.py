@@ -67,6 +67,11 @@ class ParamInfo(object):
         self.numel = int(np.prod(shape))
         self.pending_slices = 0       # column ranges of a shared 1x1 kernel whose weight gradient has not been planned yet (Plan.conv param_cols)
 
+    @property
+    def end(self):
+        """One past the parameter's last element in the arenas."""
+        return self.offset + self.numel
+
 
 class Plan(object):
     def __init__(self, batch, dtype="bf16", device="cuda", training=True):
@@ -239,6 +244,12 @@ class Plan(object):
             raise StpShapeError("slot arena exhausted")
         return self.slot_arena.data_ptr() + 8 * off, n
 
+    def _table(self, raw):
+        """A descriptor table built on the host, as a device tensor the plan keeps."""
+        dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
+        self._keep.append(dev)
+        return dev
+
     def _finish_prep(self):
         """One batched weight-preparation launch for all conv layers (descriptor table lives on the device)."""
         if self.slot_arena is not None:
@@ -251,20 +262,17 @@ class Plan(object):
         total = 0
         for i, lay in enumerate(self._prep_layers):
             total += int(self.lib.stp_weight_prepare_desc_fill(C.cast(host, C.c_void_p), i, total, *lay))
-        dev = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.device)
-        self._keep.append(dev)
+        dev = self._table(bytes(host))
         self._emit(self.prep, "stp_weight_prepare_batched", dev.data_ptr(), n, total, self.cdt)
         if self._upc_layers:      # class-collapsed weight copies of the convolutions over upsample + concat (Plan.conv)
             import struct
             assert int(self.lib.stp_weight_prepare_upcollapse_desc_bytes()) == 32
             tab = b"".join(struct.pack("<QQiiii", *lay) for lay in self._upc_layers)
-            udev = torch.frombuffer(bytearray(tab), dtype=torch.uint8).to(self.device)
-            self._keep.append(udev)
+            udev = self._table(tab)
             self._emit(self.prep, "stp_weight_prepare_upcollapse_batched", udev.data_ptr(), len(self._upc_layers), self.cdt)
             if self._upc4_layers:
                 tab4 = b"".join(struct.pack("<QQiiii", *lay) for lay in self._upc4_layers)
-                udev4 = torch.frombuffer(bytearray(tab4), dtype=torch.uint8).to(self.device)
-                self._keep.append(udev4)
+                udev4 = self._table(tab4)
                 self._emit(self.prep, "stp_weight_prepare_upcollapse_bwd_batched", udev4.data_ptr(), len(self._upc4_layers), self.cdt)
 
     # ------------------------------------------------------------------ parameters / state
@@ -291,7 +299,7 @@ class Plan(object):
     def _gptr(self, info):
         # the backward closures ask for gradient addresses in backward order: the running minimum tells the
         # data-parallel reducer which tail of the arena is final after each layer (bwd_marks)
-        self._goffs.append((info.offset, info.offset + int(np.prod(info.shape))))
+        self._goffs.append((info.offset, info.end))
         return self.G.data_ptr() + 4 * info.offset
 
     def _sptr(self, off):
@@ -313,26 +321,28 @@ class Plan(object):
         still in flight on the side stream reads that buffer (a dY aliased as a residual gradient), join first."""
         if t.grad is None:
             t.grad = self._alloc((t.N, t.H, t.W, t.gradC))
-        if self._wgroup_reads and t.grad.data_ptr() in self._wgroup_reads:
-            self._flush_wgroup()          # a pending grouped weight gradient reads this buffer as its dY: issue it first
-        if self._side_reads and t.grad.data_ptr() in self._side_reads:
-            self._mark(self.bwd, "join")
-            self._side_reads.clear()
-            self._side_groups_only = True
+        self._guard_write(t.grad)
         return t.grad
+
+    def _guard_write(self, buf):
+        """The hazard rule for a main-stream kernel about to write ``buf``."""
+        if self._wgroup_reads and buf.data_ptr() in self._wgroup_reads:
+            self._flush_wgroup()          # a pending grouped weight gradient reads this buffer as its dY: issue it first
+        if self._side_reads and buf.data_ptr() in self._side_reads:
+            self._join_side()
+
+    def _join_side(self):
+        """The main stream waits for the weight-gradient side chain: nothing in flight reads anything afterwards."""
+        self._mark(self.bwd, "join")
+        self._side_reads.clear()
+        self._side_groups_only = True
 
     def _before_inplace_write(self, buf):
         """A main-stream kernel is about to rewrite ``buf`` in place (stp_relu_bwd masks a dY): a pending grouped weight gradient
         that still reads it as its dY is issued first, a side chain in flight that reads it is joined (the rule _gradbuf applies
         to gradient buffers it hands out; advisor finding, round 3: no current network aliases such a buffer, nothing guarded it)."""
-        if buf is None:
-            return
-        if self._wgroup_reads and buf.data_ptr() in self._wgroup_reads:
-            self._flush_wgroup()
-        if self._side_reads and buf.data_ptr() in self._side_reads:
-            self._mark(self.bwd, "join")
-            self._side_reads.clear()
-            self._side_groups_only = True
+        if buf is not None:
+            self._guard_write(buf)
 
     @staticmethod
     def _use(*ts):
@@ -342,10 +352,43 @@ class Plan(object):
             if t is not None:
                 t.meta["uses"] = t.meta.get("uses", 0) + 1
 
+    # Does a launch that writes (`acc`: accumulates) its share of t's gradient complete it, so that its epilogue or pass can mask it and
+    # reduce the BatchNormalization-backward sums?  Yes for the only consumer, or the LAST of several (every other consumer has already
+    # written or accumulated its share, this one accumulates on top: STP_FUSE_BN_BACKWARD_LAST).  `promoted`: the launch carries a
+    # sibling consumer's share too, so two consumers count as one.  `last_ok`: the launch may be the accumulating last one.
+    def _completes_grad(self, t, acc, promoted=False, last_ok=True):
+        uses = t.meta.get("uses", 0)
+        sole = (uses == 1 or (promoted and uses == 2 and t.grad_writes == 1)) and not acc
+        return bool(sole or (last_ok and self.fuse_bn_backward_last and uses > 1 and t.grad_writes == uses - 1 and acc))
+
+    # A pass `fname` that writes (accumulates) its share of t's gradient: where that completes the gradient of a BatchNormalization output
+    # (and `enabled`), the pass's `_bn` form masks it and reduces the backward sums on the way (meta["bnb"] = their table and its columns)
+    def _emit_grad_pass(self, fname, t, acc, tile_args, args, enabled=True):
+        bnm = t.meta.get("bn")
+        ntl = int(getattr(self.lib, fname + "_bn_tiles")(*tile_args)) if (
+            self.fuse_bn_backward and bnm is not None and self._completes_grad(t, acc) and self.slot_arena is None and enabled) else 0
+        if ntl > 0:
+            st = self._alloc((2 * t.C * ntl,), torch.float32)
+            self._emit(self.bwd, fname + "_bn", *args, *bnm, st.data_ptr())
+            t.meta["bnb"] = (st, ntl)
+        else:
+            self._emit(self.bwd, fname, *args)
+
     # a launch record is (C function, args without the trailing stream, entry-point name, meta);
     # meta carries the layer name and the ALGORITHMIC flops of GEMM launches for bench.py's roofline.
     def _emit(self, lst, fname, *args):
         lst.append((getattr(self.lib, fname), args, fname, None))
+
+    # meta["bn"] of a BatchNormalization output = (pre-normalisation tensor, mean, rstd, gamma, beta, activation)
+    @staticmethod
+    def _set_src_bn(p, bn):
+        """The producer BatchNormalization ``bn`` as the src_bn_* operands of a ConvParams / WgradParams."""
+        p.src_bn_mean, p.src_bn_rstd, p.src_bn_gamma, p.src_bn_beta, p.src_bn_relu = bn[1:]
+
+    @staticmethod
+    def _set_bnb(q, bn):
+        """The BatchNormalization ``bn`` whose output gradient the data gradient ``q`` completes, as its bnb_* operands; None clears them."""
+        q.bnb_x, q.bnb_mean, q.bnb_rstd, q.bnb_gamma, q.bnb_beta, q.bnb_relu = bn or (None, None, None, None, None, 0)
 
     def _fuse_bn_into_consumers(self):
         """BatchNormalization(+activation) outputs that only convolutions with a fused-producer path read:
@@ -363,26 +406,19 @@ class Plan(object):
             rec, sc, halo = t.meta.get("apply_rec"), t.meta.get("sc_consumers") or [], t.meta.get("halo_consumers") or []
             if rec is None or not (sc or halo) or len(sc) + len(halo) != t.meta.get("uses", 0):
                 continue
-            pre, mean, rstd, gp, beta, relu = t.meta["bn"]
-            for cp, wp in sc:
-                cp.src0 = pre
-                cp.src_bn_mean, cp.src_bn_rstd, cp.src_bn_gamma, cp.src_bn_beta, cp.src_bn_relu = mean, rstd, gp, beta, relu
-                if not halo:       # (with halo consumers the normalised tensor exists anyway: the weight gradient reads it)
-                    wp.src_bn_mean, wp.src_bn_rstd, wp.src_bn_gamma, wp.src_bn_beta, wp.src_bn_relu = mean, rstd, gp, beta, relu
+            bn = t.meta["bn"]
             halo_full = bool(halo) and all(ok for _, _, ok in halo)      # every weight gradient fuses the BatchNormalization too
-            for cp, wp, _ in halo:
-                cp.src0 = pre
-                cp.src_bn_mean, cp.src_bn_rstd, cp.src_bn_gamma, cp.src_bn_beta, cp.src_bn_relu = mean, rstd, gp, beta, relu
-                if halo_full:
-                    wp.src_bn_mean, wp.src_bn_rstd, wp.src_bn_gamma, wp.src_bn_beta, wp.src_bn_relu = mean, rstd, gp, beta, relu
-            if halo_full:
-                for cp, wp in sc:
-                    wp.src_bn_mean, wp.src_bn_rstd, wp.src_bn_gamma, wp.src_bn_beta, wp.src_bn_relu = mean, rstd, gp, beta, relu
+            for cp, wp in sc + [h[:2] for h in halo]:
+                cp.src0 = bn[0]
+                self._set_src_bn(cp, bn)
+                # (with a halo consumer whose weight gradient cannot normalise its operand the normalised tensor exists anyway: all read it)
+                if not halo or halo_full:
+                    self._set_src_bn(wp, bn)
             if halo and not halo_full:
                 side.add(id(rec))
             else:
                 t.meta["deferred"] = rec
-                t.meta["src_override"] = pre
+                t.meta["src_override"] = bn[0]
                 drop.add(id(rec))
         if drop or side:
             # every cross-stream edge of the step graph costs a queue hand-off: the deferred launches are issued in batches
@@ -482,14 +518,19 @@ class Plan(object):
             meta = dict(meta, pw=(int(p.C0), int(p.Cout)))                  # the pointwise streaming kernel's instance <Cin, Cout, ...> (bench.py)
         lst.append((self.lib.stp_conv2d, (C.byref(p),), "stp_conv2d", meta))
 
-    def _emit_wgrad(self, lst, p, meta=None, defer_hi=0):
-        """Weight gradient = split partial sums + fixed-order reduce: two launch records so that each
-        kernel can be timed on its own (bench.py) - same arithmetic as stp_conv2d_wgrad.
+    def _emit_wgrad(self, p, name, flops, reads, defer_hi=0):
+        """The weight gradient of ONE layer, forked onto the side chain (``reads``: the dY buffers it reads): split partial sums +
+        fixed-order reduce, two launch records so that each kernel can be timed on its own (bench.py) - same arithmetic as stp_conv2d_wgrad.
         ``defer_hi`` > 0 (the end of the layer's range in the gradient arena; only when nothing reads dW before the optimizer): a layer
         with plain slabs writes them into a workspace of its own and its reduce joins the pending table (_flush_reduces)."""
+        lst = self.bwd
+        self._mark(lst, "fork")
+        self._side_groups_only = False
+        self._side_reads.update(reads)
         self._keep.append(p)
-        meta = dict(meta or {}, stream=1)
-        if defer_hi > 0 and self.reduce_batch > 0 and lst is self.bwd:
+        meta = {"layer": name, "pass": "wgrad", "flops": flops, "cout": p.Cout, "sc": bool(self.lib.stp_wgrad_sc_eligible(C.byref(p))),
+                "kernel_id": int(self.lib.stp_conv2d_wgrad_kernel_id(C.byref(p))), "stream": 1}
+        if defer_hi > 0 and self.reduce_batch > 0:
             db = int(self.lib.stp_wgrad_reduce_desc_bytes())
             wsb = int(self.lib.stp_conv2d_wgrad_workspace_bytes(C.byref(p)))
             ws = self._alloc((max(wsb // 4, 4) + 4,), torch.float32)
@@ -513,8 +554,7 @@ class Plan(object):
         if not self._pending_reduces:
             return
         table = b"".join(d for d, _ in self._pending_reduces)
-        dev = torch.frombuffer(bytearray(table), dtype=torch.uint8).to(self.device)
-        self._keep.append(dev)
+        dev = self._table(table)
         n, maxc = len(self._pending_reduces), max(c for _, c in self._pending_reduces)
         self.bwd.append((self.lib.stp_wgrad_reduce_batched, (dev.data_ptr(), n, maxc), "stp_wgrad_reduce_batched", {"stream": 1, "layers": n}))
         self._pending_reduces, self._pending_reduce_hi = [], 0
@@ -535,13 +575,7 @@ class Plan(object):
             # a lone layer gains nothing from the work list (measured on the bottleneck ResNets, whose 3x3 layers never neighbour:
             # FPN/ResNet50 1024x1024 18.25 -> 17.85 ms, PSPNet/ResNet101 768x768 10.13 -> 10.03 ms with the per-layer launch and its
             # tuned split count); the 32-channel class exists only as a grouped kernel (the per-layer one pads it to 64)
-            wp, name, flops = layers[0]
-            self._mark(self.bwd, "fork")
-            self._side_groups_only = False
-            self._side_reads.update(reads)
-            self._emit_wgrad(self.bwd, wp, {"layer": name, "pass": "wgrad", "flops": flops, "cout": wp.Cout,
-                                            "sc": bool(self.lib.stp_wgrad_sc_eligible(C.byref(wp))),
-                                            "kernel_id": int(self.lib.stp_conv2d_wgrad_kernel_id(C.byref(wp)))})
+            self._emit_wgrad(*layers[0], reads)
             return
         arr = (C.POINTER(_lib.WgradParams) * n)(*[C.pointer(wp) for wp, _, _ in layers])
         tb = int(self.lib.stp_wgrad_group_table_bytes(arr, n))
@@ -550,9 +584,9 @@ class Plan(object):
             raise StpShapeError("grouped weight gradient: the layers %s do not form a group" % [nm for _, nm, _ in layers])
         host = (C.c_char * tb)()
         _lib.check(self.lib.stp_wgrad_group_build(arr, n, C.addressof(host), tb), "stp_wgrad_group_build")
-        dev = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.device)
+        dev = self._table(bytes(host))
         ws = self._alloc((wsb // 4,), torch.float32)
-        self._keep += [arr, host, dev] + [wp for wp, _, _ in layers]
+        self._keep += [arr, host] + [wp for wp, _, _ in layers]
         names = [nm for _, nm, _ in layers]
         self.wgroups.append((names, cls))
         self._mark(self.bwd, "fork")
@@ -623,8 +657,7 @@ class Plan(object):
         beta = self.param(name + "/beta", (Cn,), "beta")
         mm = self.state(name + "/moving_mean", Cn, 0.0)
         mv = self.state(name + "/moving_variance", Cn, 1.0)
-        trainable = beta.trainable
-        out = self._new(name, x.H, x.W, Cn, x.needs_grad or trainable)
+        out = self._new(name, x.H, x.W, Cn, x.needs_grad or beta.trainable)
         self._bn_ws_c = max(self._bn_ws_c, Cn)
         self._use(x)
         if self.dry:
@@ -636,23 +669,14 @@ class Plan(object):
                        self._sptr(mm), self._sptr(mv), eps, gp, self._pptr(beta), int(relu), 0.0)
             return out
         mean, rstd = self._alloc((Cn,), torch.float32), self._alloc((Cn,), torch.float32)
-        fused = x.meta.get("stats")
+        table = x.meta.get("stats_table")      # [2][C][columns] sums and their column count: a convolution's epilogue, or Plan.se's scale-add pass
         slots = x.meta.get("stats_slots")
         if slots is not None:
             # statistics from the producing convolution's fixed-point slots: finalize + normalise + activation in one kernel
             self._emit(self.fwd, "stp_bn_apply_slots", x.buf.data_ptr(), out.buf.data_ptr(), self.cdt, x.rows, Cn, slots[0], slots[1], eps,
                        momentum, mean.data_ptr(), rstd.data_ptr(), self._sptr(mm), self._sptr(mv), gp, self._pptr(beta), int(relu))
-        elif fused is not None:
-            st, cp = fused
-            tiles = int(self.lib.stp_conv2d_stats_floats(C.byref(cp))) // (2 * Cn)
-            if x.meta.get("stats_table") is not None:
-                st, tiles = x.meta["stats_table"]
-            self._emit(self.fwd, "stp_bn_finalize", st.data_ptr(), tiles, x.rows, Cn, eps, momentum, mean.data_ptr(),
-                       rstd.data_ptr(), self._sptr(mm), self._sptr(mv))
-        elif x.meta.get("stats_table") is not None:
-            # a [2][C][columns] table that no convolution wrote (Plan.se: the scale-add pass sums the tensor it stores)
-            st, tiles = x.meta["stats_table"]
-            self._emit(self.fwd, "stp_bn_finalize", st.data_ptr(), tiles, x.rows, Cn, eps, momentum, mean.data_ptr(),
+        elif table is not None:
+            self._emit(self.fwd, "stp_bn_finalize", table[0].data_ptr(), table[1], x.rows, Cn, eps, momentum, mean.data_ptr(),
                        rstd.data_ptr(), self._sptr(mm), self._sptr(mv))
         else:
             self._emit(self.fwd, "stp_bn_stats", x.buf.data_ptr(), self.cdt, x.rows, Cn, eps, momentum, mean.data_ptr(),
@@ -663,8 +687,7 @@ class Plan(object):
         out.meta["bn"] = (x.buf.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gp, self._pptr(beta), int(relu))
         if self.fuse_bn_sc and slots is None:
             out.meta["apply_rec"] = self.fwd[-1]
-            out.meta["sc_consumers"] = []
-            out.meta["halo_consumers"] = []
+            out.meta["sc_consumers"], out.meta["halo_consumers"] = [], []
 
         def back():
             if not out.needs_grad or not out.grad_ready:
@@ -676,20 +699,15 @@ class Plan(object):
                     and out.meta.get("bnb") is not None):
                 # x's gradient so far is the dY of a convolution whose weight gradient waits in the pending group (the residual
                 # branch aliases it): accumulate OUT OF PLACE - the sum lands in a fresh buffer, the dY stays intact
-                dadd = x.grad
-                x.grad = None
+                dadd, x.grad = x.grad, None
             dx = self._gradbuf(x) if x.needs_grad else self._alloc((x.N, x.H, x.W, Cn))
             if bslots is not None:
                 self._emit(self.bwd, "stp_bn_backward_slots", x.buf.data_ptr(), out.grad.data_ptr(), dx.data_ptr(), self.cdt, x.rows, Cn,
                            mean.data_ptr(), rstd.data_ptr(), gp, bslots[0], bslots[1], self._gptr(gamma) if gamma else None,
                            self._gptr(beta), int(x.grad_ready and x.needs_grad))
-                if x.needs_grad:
-                    x.grad_ready = True
-                return
-            fused_b = out.meta.get("bnb")
-            if fused_b is not None:
+            elif out.meta.get("bnb") is not None:
                 # the only consumer's data-gradient epilogue already masked dY and reduced the per-tile sums
-                st, q = fused_b
+                st, q = out.meta["bnb"]
                 tiles = q if isinstance(q, int) else int(self.lib.stp_conv2d_stats_floats(C.byref(q))) // (2 * Cn)
                 if dadd is not None:
                     self._emit(self.bwd, "stp_bn_backward_fused_add", x.buf.data_ptr(), out.grad.data_ptr(), dx.data_ptr(), dadd.data_ptr(),
@@ -700,18 +718,21 @@ class Plan(object):
                                x.rows, Cn, mean.data_ptr(), rstd.data_ptr(), gp, st.data_ptr(), tiles,
                                self._gptr(gamma) if gamma else None, self._gptr(beta), int(x.grad_ready and x.needs_grad),
                                self.ws_bn.data_ptr(), self.ws_bn.numel() * 4)
-                if x.needs_grad:
-                    x.grad_ready = True
-                return
-            self._emit(self.bwd, "stp_bn_backward", x.buf.data_ptr(), out.grad.data_ptr(), dx.data_ptr(), self.cdt, x.rows, Cn,
-                       mean.data_ptr(), rstd.data_ptr(), gp, self._pptr(beta), self._gptr(gamma) if gamma else None,
-                       self._gptr(beta), int(relu), int(x.grad_ready and x.needs_grad), self.ws_bn.data_ptr(),
-                       self.ws_bn.numel() * 4)
+            else:
+                self._emit(self.bwd, "stp_bn_backward", x.buf.data_ptr(), out.grad.data_ptr(), dx.data_ptr(), self.cdt, x.rows, Cn,
+                           mean.data_ptr(), rstd.data_ptr(), gp, self._pptr(beta), self._gptr(gamma) if gamma else None,
+                           self._gptr(beta), int(relu), int(x.grad_ready and x.needs_grad), self.ws_bn.data_ptr(), self.ws_bn.numel() * 4)
             if x.needs_grad:
                 x.grad_ready = True
 
         self._tape.append(back)
         return out
+
+    def _emit_bias_grad(self, dy, rows, gradC, Cout, b):
+        """Bias gradient = the channel sums of ``dy`` ([rows][gradC], the first ``Cout`` channels real)."""
+        tmp = self._alloc((gradC,), torch.float32)
+        self._emit(self.bwd, "stp_channel_sum", dy.data_ptr(), self.cdt, rows, gradC, tmp.data_ptr(), 0, self.ws_bn.data_ptr(), self.ws_bn.numel() * 4)
+        self._emit(self.bwd, "stp_weight_grad_unpad", tmp.data_ptr(), self._gptr(b), Cout, 1, 1, 1, 1, 1, 0)
 
     def conv3x3_taps(self, name, x, Cout, bias=False):
         """``Conv2D(Cout, 3x3, padding 1)`` with few output channels over many input channels (the class heads of FPN / PSPNet: 512 -> 3 /
@@ -740,10 +761,7 @@ class Plan(object):
                 return
             dy = out.grad
             if b is not None and b.trainable:
-                tmp = self._alloc((out.gradC,), torch.float32)
-                self._emit(self.bwd, "stp_channel_sum", dy.data_ptr(), self.cdt, out.rows, out.gradC, tmp.data_ptr(), 0,
-                           self.ws_bn.data_ptr(), self.ws_bn.numel() * 4)
-                self._emit(self.bwd, "stp_weight_grad_unpad", tmp.data_ptr(), self._gptr(b), Cout, 1, 1, 1, 1, 1, 0)
+                self._emit_bias_grad(dy, out.rows, out.gradC, Cout, b)
             if z.needs_grad:
                 self._emit(self.bwd, "stp_tapsum_bwd", dy.data_ptr(), self._gradbuf(z).data_ptr(), self.N, x.H, x.W, Cout, out.gradC, z.gradC, self.cdt)
                 z.grad_ready = True
@@ -769,434 +787,14 @@ class Plan(object):
         convolution is a stride-1 convolution over the ZERO-INSERTED input (2H-1 x 2W-1) with pad k-1-(k/2-1) and the
         spatially flipped kernel - the zero-insertion gather that the stride-2 data-gradients already use.  The master
         parameter holds the flipped OHWI kernel (kind "tkernel"; set/get_weights convert from Keras' (kh,kw,out,in))."""
-        if transpose:
-            if stride != 1 or upsample or src1 is not None or residual is not None or k % 2:
-                raise StpShapeError("transpose=True is the plain stride-2 'same' Conv2DTranspose with an even kernel")
-            pad = k - 1 - (k // 2 - 1)
-        real_c0 = x.meta.get("real_c", x.C)
-        stem = real_c0 != x.C
-        if stem and (src1 is not None or upsample):
-            raise StpShapeError("padded-channel input supports a plain conv only")
-        C0, C1 = x.C, (src1.C if src1 is not None else 0)
-        if not stem and (C0 % self.vec or C1 % self.vec):
-            raise StpShapeError("%s: input channels (%d,%d) must be multiples of %d for dtype %s" % (name, C0, C1, self.vec, self.dtype))
-        Hv, Wv = (2 * x.H, 2 * x.W) if upsample else ((2 * x.H - 1, 2 * x.W - 1) if transpose else (x.H, x.W))
-        if src1 is not None and (src1.H, src1.W) != (Hv, Wv):
-            raise StpShapeError("%s: skip tensor is %dx%d, expected %dx%d" % (name, src1.H, src1.W, Hv, Wv))
-        Ho, Wo = (Hv + 2 * pad - k) // stride + 1, (Wv + 2 * pad - k) // stride + 1
-        if same_tf:
-            # TF / Keras padding='same': ceil(size / stride) outputs, the odd padding pixel goes to the bottom / right.  The
-            # kernels take the top/left padding and the output size; taps past the far edge are out of bounds = zero.
-            Ho, Wo = -(-Hv // stride), -(-Wv // stride)
-            pad = max((Ho - 1) * stride + k - Hv, 0) // 2
-            if max((Wo - 1) * stride + k - Wv, 0) // 2 != pad:
-                raise StpShapeError("%s: 'same' padding differs between height and width" % name)
-        KWp = k + (k & 1) if (stem and x.C == 4) else k      # 4 padded channels: one 16-byte vector = two horizontally adjacent taps
-        Cin_master = real_c0 + C1
-        Cinp = C0 + C1
-        # (param_name / param_shape: conv3x3_taps - the 1x1 launch over the bytes of a 3x3 kernel registered under the layer's own name)
-        if param_cols is not None:
-            if k != 1 or stem or transpose or C1 or Cout % self.vec or Cin_master % 4 or param_cols[0] % 4 or param_cols[1] % 4 \
-                    or param_cols[0] + Cin_master > param_cols[1]:
-                raise StpShapeError("%s: a column range of a shared kernel serves a plain 1x1 convolution with aligned channel counts" % name)
-            param_shape = None
-        w = self.param((param_name or name) + "/kernel", (Cout, 1, 1, param_cols[1]) if param_cols is not None else (param_shape or (Cout, k, k, Cin_master)),
-                       "tkernel" if transpose else "kernel")
-        if param_shape is not None and int(np.prod(param_shape)) != Cout * k * k * Cin_master:
-            raise StpShapeError("%s: parameter view of %s does not match %d x %d x %d x %d" % (name, param_shape, Cout, k, k, Cin_master))
-        b = self.param(name + "/bias", (Cout,), "bias") if bias else None
-        CoutB = _rup(Cout, cout_pad or self.vec)      # channels of the gradient buffer = K of the data gradient (cout_pad: conv3x3_taps)
-        x_ng = x.needs_grad
-        s_ng = src1.needs_grad if src1 is not None else False
-        out = self._new(name, Ho, Wo, Cout, x_ng or s_ng or w.trainable or (residual is not None and residual.needs_grad))
-        out.gradC = CoutB
-        if bias:
-            self._bn_ws_c = max(self._bn_ws_c, CoutB)      # the bias gradient (stp_channel_sum) shares the BN workspace
-        self._use(x, src1, residual)
-        # workspace sizing needs the wgrad plan: query the library (cheap, host only)
-        wp = _lib.WgradParams()
-        wp.N, wp.Hs0, wp.Ws0, wp.Hv, wp.Wv, wp.C0, wp.C1 = self.N, x.H, x.W, Hv, Wv, C0, C1
-        src_mode = ops.SRC_NEAREST2X if upsample else (ops.SRC_ZEROINS2X if transpose else ops.SRC_DIRECT)
-        wp.src0_mode = src_mode
-        wp.KH, wp.KW, wp.stride, wp.pad, wp.Ho, wp.Wo, wp.Cout = k, KWp, stride, pad, Ho, Wo, CoutB
-        wp.accumulate, wp.dtype, wp.splits = 0, self.cdt, 0
-        if self.training and w.trainable:
-            self._wg_ws_bytes = max(self._wg_ws_bytes, int(self.lib.stp_conv2d_wgrad_workspace_bytes(C.byref(wp))))
+        L = ConvLayer(self, name, x, Cout, k, stride, pad, src1, upsample, residual, transpose, relu, same_tf, fold_shortcut, param_cols)
+        L.declare(param_name, param_shape, cout_pad, bias)
         if self.dry:
-            return out
-        rows_f, rows_b = _rup(Cout, 16), _rup(Cinp, 16)
-        wf = self._alloc((rows_f * k * KWp * Cinp,))
-        need_dgrad = self.training and (x_ng or s_ng) and not stem
-        wb = self._alloc((rows_b * k * k * CoutB,)) if need_dgrad else None
-        out.meta["wb"] = wb
-        wsrc = self._pptr(w)
-        if param_cols is not None:
-            w.pending_slices += 1      # (backward: the LAST range written makes the parameter's gradient final)
-            # the column range as a dense [Cout][Cin] fp32 matrix, refreshed every step in front of the batched weight preparation
-            wm = self._alloc((Cout * Cin_master,), torch.float32)
-            self._emit(self.prep, "stp_copy_cols_f32", wm.data_ptr(), Cin_master, wsrc + 4 * int(param_cols[0]), int(param_cols[1]), Cout, Cin_master, 0)
-            wsrc = wm.data_ptr()
-        out.meta["w_master"] = (wsrc, Cout, Cin_master, k)      # (the space-to-depth data gradient builds its weights from the masters)
-        # collected here, issued as ONE batched launch per step (see _finish_prep)
-        self._prep_layers.append((wsrc, wf.data_ptr(), wb.data_ptr() if wb is not None else None,
-                                  Cout, k, k, Cin_master, KWp, Cinp, CoutB))
-        p = ops.conv_params(x.buf, wf, out.buf, N=self.N, Hs0=x.H, Ws0=x.W, Hv=Hv, Wv=Wv, C0=C0, C1=C1,
-                            src1=src1.buf if src1 is not None else None,
-                            mode=src_mode, KH=k, KW=KWp, stride=stride, pad=pad,
-                            Ho=Ho, Wo=Wo, Cout=Cout, dtype=self.cdt, residual=residual.buf if residual is not None else None)
-        w4 = None
-        if (upsample and src1 is not None and k == 3 and KWp == 3 and stride == 1 and pad == 1 and Cinp == Cin_master == C0 + C1
-                and os.environ.get("STP_UPCOLLAPSE", "1") != "0" and not self.lib.stp_conv2d_scn_eligible(C.byref(p))
-                and int(self.lib.stp_conv2d_halo_variant(C.byref(p))) < 0):
-            # (the narrow-output kernel - 64 + 64 -> 32 channels - keeps both halos in LDS and takes the plain weight copy; so does the
-            #  two-source form of the halo kernel, round 5: 128+ output channels)
-            # decoder conv1 = conv3x3(concat(UpSampling2D(2)(x), skip)): per output parity class the taps over the upsampled half read
-            # 2 x 2 low-resolution pixels - the forward multiplies them by class-summed weights (4 x C0 + 9 x C1 K columns instead
-            # of 9 x (C0 + C1)); the summed copy is rebuilt from the fp32 master with the other weight copies, once per step
-            wup = self._alloc((rows_f * 16 * C0,))
-            self._upc_layers.append((self._pptr(w), wup.data_ptr(), Cout, rows_f, C0, C0 + C1))     # one batched launch (_finish_prep)
-            p.weight_up = wup.data_ptr()
-            if need_dgrad and x_ng and C0 % 16 == 0 and os.environ.get("STP_UPCOLLAPSE_BWD", "0") == "1":
-                # ... and the data gradient w.r.t. x is a 4x4 / stride-2 convolution of dY with the row / column tap sums.  OPT-IN:
-                # measured slower with today's kernels for the two resulting shapes (DESIGN.md), kept for the next round
-                w4 = self._alloc((C0 * 16 * CoutB,))
-                self._upc4_layers.append((self._pptr(w), w4.data_ptr(), Cout, CoutB, C0, C0 + C1))
-        if (self.training and x.meta.get("apply_rec") is not None and src1 is None and residual is None and not transpose and not stem
-                and self.lib.stp_conv2d_sc_eligible(C.byref(p)) and (not w.trainable or self.lib.stp_wgrad_sc_eligible(C.byref(wp)))):
-            x.meta["sc_consumers"].append((p, wp))       # see _fuse_bn_into_consumers
-        elif (self.training and self.fuse_bn_halo and x.meta.get("apply_rec") is not None and src1 is None and not transpose and not stem
-                and not upsample and self.lib.stp_conv2d_halo_variant(C.byref(p)) >= 0):
-            # (p, wp, can the weight gradient normalise its operand itself: row-of-taps kernel - or no weight gradient at all)
-            x.meta["halo_consumers"].append((p, wp, (not w.trainable) or int(self.lib.stp_conv2d_wgrad_kernel_id(C.byref(wp))) in (2, 3)))
-        if b is not None:
-            p.bias = self._pptr(b)
-        if relu:
-            if CoutB != Cout:
-                raise StpShapeError("%s: a fused ReLU needs Cout to be a multiple of %d" % (name, self.vec))
-            p.relu = 1        # Conv2D(activation='relu'): fused into the epilogue; its gradient masks dY first (stp_relu_bwd)
-        if bn_stats and self.training and self.slot_arena is not None and self.N * Ho * Wo <= self.bn_slots_max_rows:
-            sp, sn = self._slots(Cout)
-            p.stats_partial, p.stats_slots = sp, sn
-            out.meta["stats_slots"] = (sp, sn)
-        elif bn_stats and self.training:
-            # the BatchNormalization that follows takes its batch statistics from this conv's epilogue
-            nfl = int(self.lib.stp_conv2d_stats_floats(C.byref(p)))
-            st = self._alloc((max(nfl, 4),), torch.float32)
-            p.stats_partial = st.data_ptr()
-            out.meta["stats"] = (st, p)
-            out.meta["stats_table"] = self._group_stats(p, st, Cout)       # (table, columns) the BatchNormalization reads
-        # algorithmic work of this layer: 2 * pixels * Cout * KH*KW*Cin with the REAL (unpadded) dims
-        flops = 2.0 * self.N * Ho * Wo * Cout * k * k * Cin_master / (4.0 if transpose else 1.0)   # zero-inserted taps are not work
-        if flops_as is not None:
-            # (a launch of a RESTRUCTURED reference layer - the PSPNet head without its concatenation: the roofline bookkeeping keeps
-            #  counting the reference graph's convolution, SURVEY 8d's convention, not the cheaper form that is executed)
-            flops = float(flops_as)
-        self._emit_conv(self.fwd, p, {"layer": name, "pass": "fwd", "flops": flops, "tile": int(self.lib.stp_conv2d_tile_for(C.byref(p))),
-                                      "src2": bool(C1 or upsample)})
-        if not self.training:
-            return out
-
-        def back():
-            if not out.needs_grad or not out.grad_ready:
-                return
-            dy = out.grad
-            rows = out.rows
-            if relu:
-                self._before_inplace_write(dy)
-                self._emit(self.bwd, "stp_relu_bwd", out.buf.data_ptr(), dy.data_ptr(), rows * out.gradC, self.cdt)
-            # lag-1 join: the previous convolution's weight-gradient chain finishes before this layer's kernels start.
-            # (Letting the side chain fall further behind - joining only on a buffer hazard, see _gradbuf - measured
-            # SLOWER, 11.15 vs 10.88 ms/step: the chain then reads dY / x long after the main chain left them in L2.)
-            if self._side_lag_join or not self._side_groups_only:
-                self._mark(self.bwd, "join")
-                self._side_reads.clear()
-                self._side_groups_only = True
-            # residual branch: d(residual) = dY
-            if residual is not None and residual.needs_grad:
-                if not residual.grad_ready and residual.gradC == out.gradC:
-                    residual.grad = dy          # alias: dY is dead once this layer's backward has been issued
-                    residual.grad_ready = True
-                else:
-                    self._emit(self.bwd, "stp_add_inplace", self._gradbuf(residual).data_ptr(), dy.data_ptr(),
-                               rows * out.gradC, self.cdt)
-            # weight gradient: on the side stream, forked here (dY is final); joined before any kernel rewrites dY (_gradbuf)
-            # and at the end of the launch list
-            if w.trainable:
-                padded = stem or CoutB != Cout
-                gcols = None
-                if padded:
-                    dwp = self._alloc((CoutB * k * KWp * Cinp,), torch.float32)
-                    wp.dw = dwp.data_ptr()
-                elif param_cols is not None:
-                    gcols = self._alloc((Cout * Cin_master,), torch.float32)       # dense gradient of the column range, copied back below
-                    wp.dw = gcols.data_ptr()
-                else:
-                    wp.dw = self._gptr(w)
-                wp.src0, wp.src1, wp.dy = x.meta.get("src_override") or x.buf.data_ptr(), (src1.buf.data_ptr() if src1 is not None else None), dy.data_ptr()
-                cls = int(self.lib.stp_wgrad_group_class(C.byref(wp))) if (self.wgrad_group_gflop > 0 and not padded and gcols is None) else 0
-                if cls:
-                    # row-of-taps layer: joins the pending group (one launch per stage instead of one per layer); dY stays untouched
-                    # until the group is issued (_gradbuf / the BatchNormalization backward's out-of-place accumulate see to that)
-                    if self._wgroup and self._wgroup_cls != cls:
-                        self._flush_wgroup()
-                    self._wgroup.append((wp, name, flops))
-                    self._wgroup_cls = cls
-                    self._wgroup_flops += flops
-                    self._wgroup_hi = max(self._wgroup_hi, w.offset + int(np.prod(w.shape)))
-                    self._wgroup_reads.add(dy.data_ptr())
-                    if self._wgroup_flops >= self.wgrad_group_gflop * 1e9:
-                        self._flush_wgroup()
-                else:
-                    # a layer outside the groups (stride 2, 1x1, stem, small-channel): the pending group is issued first, so a group
-                    # = consecutive row-of-taps layers (a network stage) and the gradient arena stays final above the last visited layer
-                    self._flush_wgroup()
-                    self._mark(self.bwd, "fork")
-                    self._side_groups_only = False
-                    self._side_reads.add(dy.data_ptr())     # see _gradbuf: the only buffer of the chain that is ever rewritten
-                    self._emit_wgrad(self.bwd, wp, {"layer": name, "pass": "wgrad", "flops": flops, "cout": CoutB,
-                                                    "sc": bool(self.lib.stp_wgrad_sc_eligible(C.byref(wp))),
-                                                    "kernel_id": int(self.lib.stp_conv2d_wgrad_kernel_id(C.byref(wp)))},
-                                     defer_hi=0 if (padded or gcols is not None) else w.offset + int(np.prod(w.shape)))       # (a padded dW is unpadded right below)
-                if gcols is not None:
-                    # (the arena range of the shared kernel is reported final - _gptr, bwd_marks - by the last of its ranges only)
-                    w.pending_slices -= 1
-                    gbase = self._gptr(w) if w.pending_slices == 0 else self.G.data_ptr() + 4 * w.offset
-                    self._emit_side(self.bwd, "stp_copy_cols_f32", gbase + 4 * int(param_cols[0]), int(param_cols[1]), gcols.data_ptr(), Cin_master,
-                                    Cout, Cin_master, 0)
-                if padded:
-                    self._emit_side(self.bwd, "stp_weight_grad_unpad", dwp.data_ptr(), self._gptr(w), Cout, k, k, Cin_master, KWp,
-                                    Cinp, 0)
-                beta = x.meta.get("input_bn_beta")
-                if stem and beta is not None and beta.trainable:
-                    self._emit_side(self.bwd, "stp_stem_beta_grad", dwp.data_ptr(), self._pptr(w), self._gptr(beta), Cout, k, k,
-                               real_c0, KWp, Cinp, real_c0)
-            if b is not None and b.trainable and out.meta.get("loss_bias_grad") and Cout == 1:
-                # the 1-class head: the loss gradient kernel left the per-workgroup sums of dL/dlogit in its workspace
-                self._emit(self.bwd, "stp_sigmoid_loss_bias_grad", self.ws_loss.data_ptr(), rows, self._gptr(b), 0)
-            elif b is not None and b.trainable and out.meta.get("loss_bias_grad") == "multilabel":
-                # the multi-label head: one partial sum per class and gradient workgroup, left by stp_sigmoid_multilabel_loss
-                self._emit(self.bwd, "stp_sigmoid_multilabel_bias_grad", self.ws_loss.data_ptr(), rows, Cout, self._gptr(b), 0)
-            elif b is not None and b.trainable:
-                tmp = self._alloc((CoutB,), torch.float32)
-                self._emit(self.bwd, "stp_channel_sum", dy.data_ptr(), self.cdt, rows, CoutB, tmp.data_ptr(), 0,
-                           self.ws_bn.data_ptr(), self.ws_bn.numel() * 4)
-                self._emit(self.bwd, "stp_weight_grad_unpad", tmp.data_ptr(), self._gptr(b), Cout, 1, 1, 1, 1, 1, 0)
-            # data gradient
-            if need_dgrad and out.meta.get("dgrad_folded"):
-                pass        # a projection shortcut whose data gradient rode in its sibling's launch (fold_shortcut): nothing to issue
-            elif need_dgrad:
-                d0_hires = None
-                if upsample:
-                    d0 = d0_hires = self._alloc((self.N, Hv, Wv, C0)) if x_ng else None      # released below when the launch folds the 2 x 2 sums
-                    acc0 = 0
-                else:
-                    d0 = self._gradbuf(x) if x_ng else None
-                    acc0 = int(x.grad_ready)
-                d1 = self._gradbuf(src1) if s_ng else None
-                acc1 = int(src1.grad_ready) if s_ng else 0
-                if d0 is None:
-                    d0 = self._alloc((self.N, Hv, Wv, C0))      # gradient not wanted: scratch sink
-                if C1 and d1 is None:
-                    d1 = self._alloc((self.N, Hv, Wv, C1))
-                if transpose:
-                    # gradient of the zero-inserted input at its even positions only = a plain stride-2 convolution of dY
-                    q = ops.conv_params(dy, wb, d0, N=self.N, Hs0=Ho, Ws0=Wo, Hv=Ho, Wv=Wo, C0=CoutB, mode=ops.SRC_DIRECT, KH=k, KW=k,
-                                        stride=2, pad=k - 1 - pad, Ho=x.H, Wo=x.W, Cout=C0, dtype=self.cdt, accumulate0=acc0)
-                else:
-                    q = ops.conv_params(dy, wb, d0, N=self.N, Hs0=Ho, Ws0=Wo,
-                                        Hv=(2 * Ho - 1 if stride == 2 else Ho), Wv=(2 * Wo - 1 if stride == 2 else Wo),
-                                        C0=CoutB, mode=(ops.SRC_ZEROINS2X if stride == 2 else ops.SRC_DIRECT), KH=k, KW=k, stride=1,
-                                        pad=k - 1 - pad, Ho=Hv, Wo=Wv, Cout=C0 + C1, dtype=self.cdt, dst1=d1, Cd0=C0,
-                                        accumulate0=acc0, accumulate1=acc1)
-                if stride not in (1, 2):
-                    raise StpShapeError("data gradient supports stride 1 and 2")
-                if (stride == 2 and k == 1 and pad == 0 and not transpose and not upsample and src1 is None and x_ng and fold_shortcut is None
-                        and C0 % 4 == 0 and os.environ.get("STP_SCATTER_1X1S2", "1") != "0"):
-                    # 1x1 / stride 2 (the projection shortcut of a bottleneck ResNet's first unit): the zero-inserted form above runs the GEMM
-                    # over all four parity classes of the high-resolution grid (229 us for 256 <- 512 channels at 4 x 256 x 256).  Instead:
-                    # t = W^T dY at LOW resolution (a plain 1x1 / stride-1 launch), then one pass that puts t at the even positions of the
-                    # gradient - and, when that completes the gradient of a BatchNormalization output, masks it and reduces the sums
-                    t_low = self._alloc((self.N, Ho, Wo, C0))
-                    qg = ops.conv_params(dy, wb, t_low, N=self.N, Hs0=Ho, Ws0=Wo, Hv=Ho, Wv=Wo, C0=CoutB, mode=ops.SRC_DIRECT, KH=1, KW=1,
-                                         stride=1, pad=0, Ho=Ho, Wo=Wo, Cout=C0, dtype=self.cdt)
-                    self._emit_conv(self.bwd, qg, {"layer": name, "pass": "dgrad", "flops": 2.0 * self.N * Ho * Wo * Cout * Cin_master,
-                                                   "tile": int(self.lib.stp_conv2d_tile_for(C.byref(qg)))})
-                    uses, bnm = x.meta.get("uses", 0), x.meta.get("bn")
-                    done = (uses == 1 and not acc0) or (self.fuse_bn_backward_last and uses > 1 and x.grad_writes == uses - 1 and acc0)
-                    ntl = int(self.lib.stp_scatter2x_bwd_bn_tiles(self.N, x.H, x.W, C0, self.cdt)) if (
-                        self.fuse_bn_backward and bnm is not None and done and self.slot_arena is None) else 0
-                    if ntl > 0:
-                        st = self._alloc((2 * C0 * ntl,), torch.float32)
-                        self._emit(self.bwd, "stp_scatter2x_bwd_bn", t_low.data_ptr(), d0.data_ptr(), self.N, x.H, x.W, C0, self.cdt, acc0,
-                                   bnm[0], bnm[1], bnm[2], bnm[3], bnm[4], bnm[5], st.data_ptr())
-                        x.meta["bnb"] = (st, ntl)
-                    else:
-                        self._emit(self.bwd, "stp_scatter2x_bwd", t_low.data_ptr(), d0.data_ptr(), self.N, x.H, x.W, C0, self.cdt, acc0)
-                    x.grad_ready = True
-                    return
-                fs = fold_shortcut
-                s2d = False
-                if (stride == 2 and k == 3 and pad == 1 and not transpose and src1 is None and x_ng and self.dtype != "fp32" and not stem
-                        and Cout == CoutB and C0 == Cin_master and (Hv, Wv) == (2 * Ho, 2 * Wo) and os.environ.get("STP_S2D", "1") != "0"
-                        and os.environ.get("STP_HALO", "1") != "0"):      # (stp_conv2d_halo_variant ignores the A/B switch; the dispatcher honours it)
-                    # SPACE-TO-DEPTH form (round 5, stp_conv_params.s2d_dgrad): the four output parity classes as ONE dense 2 x 2-tap
-                    # convolution of dY into 4 x C0 class-major channels on the halo kernel, stored depth-to-space; the sibling 1x1 /
-                    # stride-2 shortcut's dY rides along as a second source (its weights live at class 0 / tap 0 only)
-                    fold = (fs is not None and fs.needs_grad and fs.grad_ready and fs.meta.get("wb") is not None and fs.gradC == CoutB
-                            and (fs.H, fs.W) == (Ho, Wo) and fs.meta.get("w_master", (0, 0, 0, 0))[1:] == (Cout, C0, 1))
-                    qs = ops.conv_params(dy, dy, d0, N=self.N, Hs0=Ho, Ws0=Wo, Hv=Ho, Wv=Wo, C0=CoutB, C1=(CoutB if fold else 0),
-                                         src1=(fs.grad if fold else None), mode=ops.SRC_DIRECT, KH=2, KW=2, stride=1, pad=0, Ho=Ho, Wo=Wo,
-                                         Cout=4 * C0, dtype=self.cdt, accumulate0=acc0)
-                    qs.s2d_dgrad = 1
-                    qs.weight = wb.data_ptr()                   # the ordinary data-gradient copies: the kernel addresses them per parity class
-                    if fold:
-                        qs.fold_weight = fs.meta["wb"].data_ptr()
-                    if int(self.lib.stp_conv2d_halo_variant(C.byref(qs))) >= 0:
-                        q, s2d = qs, True
-                        if fold:
-                            fs.meta["dgrad_folded"] = True
-                            x.grad_writes += 1          # its share of x's gradient arrives with this launch
-                if (not s2d and fs is not None and stride == 2 and k == 3 and not transpose and src1 is None and x_ng and fs.needs_grad and fs.grad_ready
-                        and fs.meta.get("wb") is not None and fs.gradC == CoutB and (fs.H, fs.W) == (Ho, Wo)
-                        and int(self.lib.stp_conv2d_fold_ok(C.byref(q)))):
-                    # the shortcut's 1x1 / stride-2 data gradient = one more (centre) tap of this launch's (even, even) parity class
-                    q.fold_src, q.fold_weight, q.fold_C = fs.grad.data_ptr(), fs.meta["wb"].data_ptr(), CoutB
-                    fs.meta["dgrad_folded"] = True
-                    x.grad_writes += 1          # its share of x's gradient arrives with this launch
-                folded1 = False
-                if (fs is not None and stride == 1 and k == 3 and pad == 1 and not transpose and not upsample and src1 is None and x_ng
-                        and fs.needs_grad and fs.grad_ready and fs.meta.get("wb") is not None and (fs.H, fs.W) == (Ho, Wo)
-                        and fs.meta.get("w_master", (0, 0, 0, 0))[2:] == (C0, 1) and self.dtype != "fp32" and os.environ.get("STP_HALO", "1") != "0"):
-                    # the sibling 1x1 / stride-1 shortcut (first unit of ResNet18 / 34's stage 1): its dY is a second source of this launch
-                    # whose centre tap carries the shortcut's weights (conv_halo.hip, FOLD1) - no separate launch accumulates into dX
-                    q.fold_src, q.fold_weight, q.fold_C = fs.grad.data_ptr(), fs.meta["wb"].data_ptr(), fs.gradC
-                    if int(self.lib.stp_conv2d_halo_variant(C.byref(q))) >= 0:
-                        folded1 = True
-                        fs.meta["dgrad_folded"] = True
-                        x.grad_writes += 1          # its share of x's gradient arrives with this launch
-                    else:
-                        q.fold_src = q.fold_weight = None
-                        q.fold_C = 0
-                bnm = x.meta.get("bn")
-                folded_up = False
-                qC1 = C1
-                if w4 is not None:
-                    # conv3x3(concat(UpSampling2D(2)(x), skip)): the skip gradient is the plain 3x3 data gradient with the skip's rows
-                    # of the flipped weight copy; the gradient of x is a 4x4 / stride-2 convolution of dY with the tap sums (w4) that
-                    # lands on the low-resolution tensor directly - no high-resolution gradient, no stp_upsample2x_bwd
-                    if s_ng:
-                        q1 = ops.conv_params(dy, wb, d1, N=self.N, Hs0=Ho, Ws0=Wo, Hv=Ho, Wv=Wo, C0=CoutB, mode=ops.SRC_DIRECT, KH=k, KW=k,
-                                             stride=1, pad=k - 1 - pad, Ho=Hv, Wo=Wv, Cout=C1, dtype=self.cdt, accumulate0=acc1)
-                        q1.weight = wb.data_ptr() + C0 * k * k * CoutB * wb.element_size()
-                        self._emit_conv(self.bwd, q1, {"layer": name, "pass": "dgrad", "flops": flops * C1 / float(C0 + C1),
-                                                       "tile": int(self.lib.stp_conv2d_tile_for(C.byref(q1)))})
-                    q = ops.conv_params(dy, w4, self._gradbuf(x), N=self.N, Hs0=Ho, Ws0=Wo, Hv=Ho, Wv=Wo, C0=CoutB, mode=ops.SRC_DIRECT,
-                                        KH=4, KW=4, stride=2, pad=1, Ho=x.H, Wo=x.W, Cout=C0, dtype=self.cdt, accumulate0=int(x.grad_ready))
-                    folded_up, qC1 = True, 0
-                qflops = flops * (C0 - 0.0) / (C0 + C1) if w4 is not None else flops
-                if upsample and x_ng and C1 == 0 and self.fold_upsample_grad:
-                    # the small-channel kernel sums each 2x2 block in its epilogue: the hi-res gradient of the upsampled
-                    # tensor is never written and stp_upsample2x_bwd disappears
-                    q.dst_sum2x2 = 1
-                    if self.lib.stp_conv2d_sc_eligible(C.byref(q)) and C0 % 4 == 0:
-                        folded_up = True
-                        q.dst0 = self._gradbuf(x).data_ptr()
-                        q.accumulate0 = int(x.grad_ready)
-                    else:
-                        q.dst_sum2x2 = 0
-                        # the halo kernel's summed epilogue (EP 3) for 64+ channels - in its fused form only (see the two-destination case below)
-                        if (self.fuse_bn_backward and bnm is not None and x.meta.get("uses", 0) == 1 and not x.grad_ready
-                                and self.slot_arena is None and os.environ.get("STP_HALO_FOLD_UP", "1") != "0"
-                                and os.environ.get("STP_HALO", "1") != "0"):      # (the dispatcher honours STP_HALO=0: plan and dispatcher agree)
-                            keep = (q.dst0, q.accumulate0)
-                            q.dst_sum2x2, q.dst0, q.accumulate0 = 1, self._gradbuf(x).data_ptr(), 0
-                            q.bnb_x, q.bnb_mean, q.bnb_rstd, q.bnb_gamma, q.bnb_beta, q.bnb_relu = bnm
-                            if int(self.lib.stp_conv2d_halo_variant(C.byref(q))) >= 0:
-                                folded_up = True
-                            else:
-                                q.dst_sum2x2, (q.dst0, q.accumulate0) = 0, keep
-                                q.bnb_x = q.bnb_mean = q.bnb_rstd = q.bnb_gamma = q.bnb_beta = None
-                                q.bnb_relu = 0
-                two_dest = False
-                if upsample and x_ng and C1 and w4 is None and self.fold_upsample_grad:
-                    # ... and the wide-output kernel does the same for conv3x3(concat(UpSampling2D(2)(x), skip)): the first C0
-                    # channels are summed into the low-resolution gradient, the skip's C1 channels stay at full resolution
-                    q.dst_sum2x2 = 1
-                    if self.lib.stp_conv2d_scw_eligible(C.byref(q)):
-                        folded_up = two_dest = True
-                        q.dst0 = self._gradbuf(x).data_ptr()
-                        q.accumulate0 = int(x.grad_ready)
-                    else:
-                        q.dst_sum2x2 = 0
-                        # ... and the halo kernel (64+ channel decoder stages, round 4): its epilogue sums the 2 x 2 blocks of the channel
-                        # tiles of the upsampled source and runs the fused BatchNormalization backward on the LOW-resolution result
-                        # (EP 3) - only in that fused form, i.e. when this launch completes the gradient of a BatchNormalization output
-                        # that nothing else reads
-                        if (self.fuse_bn_backward and bnm is not None and x.meta.get("uses", 0) == 1 and not x.grad_ready
-                                and self.slot_arena is None and os.environ.get("STP_HALO_FOLD_UP", "1") != "0"
-                                and os.environ.get("STP_HALO", "1") != "0"):      # (the dispatcher honours STP_HALO=0: plan and dispatcher agree)
-                            keep = (q.dst0, q.accumulate0)
-                            q.dst_sum2x2, q.dst0, q.accumulate0 = 1, self._gradbuf(x).data_ptr(), 0
-                            q.bnb_x, q.bnb_mean, q.bnb_rstd, q.bnb_gamma, q.bnb_beta, q.bnb_relu = bnm
-                            if int(self.lib.stp_conv2d_halo_variant(C.byref(q))) >= 0:
-                                folded_up = two_dest = True
-                            else:
-                                q.dst_sum2x2, (q.dst0, q.accumulate0) = 0, keep
-                                q.bnb_x = q.bnb_mean = q.bnb_rstd = q.bnb_gamma = q.bnb_beta = None
-                                q.bnb_relu = 0
-                if folded_up and d0_hires is not None:
-                    # the full-resolution gradient of the upsampled tensor is never written: give its buffer back (33-134 MB per decoder
-                    # stage at batch 16, 512 x 512 - it used to stay allocated for the life of the plan)
-                    self._keep = [t for t in self._keep if t is not d0_hires]
-                    d0_hires = None
-                uses = x.meta.get("uses", 0)
-                # the only consumer, or the LAST of several (every other consumer has already written or accumulated its
-                # share, this data gradient accumulates on top): its epilogue sees the complete gradient of the BN output
-                sole = uses == 1 and not q.accumulate0
-                last = self.fuse_bn_backward_last and uses > 1 and x.grad_writes == uses - 1 and q.accumulate0 and not upsample
-                if (folded1 or s2d) and uses == 2 and x.grad_writes == 1 and not q.accumulate0:
-                    sole = True       # this launch and the sibling folded into it are the only two consumers: the gradient is complete
-                if (self.fuse_bn_backward and bnm is not None and (sole or last) and (folded_up or not upsample) and (qC1 == 0 or two_dest)
-                        and x_ng and C0 % 4 == 0):
-                    q.bnb_x, q.bnb_mean, q.bnb_rstd, q.bnb_gamma, q.bnb_beta, q.bnb_relu = bnm
-                    if self.slot_arena is not None and self.N * Hv * Wv <= self.bn_slots_max_rows and not two_dest:
-                        # (the two-destination kernel has no slot form - stp_conv2d_scw_eligible was checked without them, and with
-                        #  slots the launch would fall through to the generic kernel, which refuses dst_sum2x2: float partial sums there)
-                        sp, sn = self._slots(C0)
-                        q.stats_partial, q.stats_slots = sp, sn
-                        x.meta["bnb_slots"] = (sp, sn)
-                    else:
-                        nfl = int(self.lib.stp_conv2d_stats_floats(C.byref(q)))
-                        st = self._alloc((max(nfl, 4),), torch.float32)
-                        q.stats_partial = st.data_ptr()
-                        x.meta["bnb"] = (st, q)
-                        gt, gcols = self._group_stats(q, st, C0)
-                        if gt is not st:
-                            x.meta["bnb"] = (gt, gcols)           # the pre-reduced table ([2][C0][columns / G]) and its column count
-                self._emit_conv(self.bwd, q, {"layer": name, "pass": "dgrad", "flops": qflops,
-                                              "tile": int(self.lib.stp_conv2d_tile_for(C.byref(q))), "s2d": s2d, "fold1": folded1})
-                if upsample and x_ng and not folded_up:
-                    acc_up = int(x.grad_ready)
-                    done = (uses == 1 and not acc_up) or (self.fuse_bn_backward_last and uses > 1 and x.grad_writes == uses - 1 and acc_up)
-                    ntl = int(self.lib.stp_upsample2x_bwd_bn_tiles(self.N, x.H, x.W, C0, C0, self.cdt)) if (
-                        self.fuse_bn_backward and bnm is not None and done and self.slot_arena is None
-                        and os.environ.get("STP_FUSE_UP_BN", "1") != "0") else 0
-                    if ntl > 0:
-                        # the upsampling gradient completes dY of a BatchNormalization output: mask + backward sums in the same pass
-                        st = self._alloc((2 * C0 * ntl,), torch.float32)
-                        self._emit(self.bwd, "stp_upsample2x_bwd_bn", d0.data_ptr(), self._gradbuf(x).data_ptr(), self.N, x.H, x.W,
-                                   C0, C0, self.cdt, acc_up, bnm[0], bnm[1], bnm[2], bnm[3], bnm[4], bnm[5], st.data_ptr())
-                        x.meta["bnb"] = (st, ntl)
-                    else:
-                        self._emit(self.bwd, "stp_upsample2x_bwd", d0.data_ptr(), self._gradbuf(x).data_ptr(), self.N, x.H, x.W,
-                                   C0, C0, self.cdt, acc_up)
-                if x_ng:
-                    x.grad_ready = True
-                if s_ng:
-                    src1.grad_ready = True
-
-        self._tape.append(back)
-        return out
+            return L.out
+        L.forward(bn_stats, flops_as)
+        if self.training:
+            self._tape.append(L.backward)
+        return L.out
 
     def add(self, name, y, skip):
         """Keras ``Add()([y, skip])`` computed in place on y's buffer (y must have no other consumer): Linknet's
@@ -1747,21 +1345,11 @@ class Plan(object):
             if not (x.needs_grad and out.grad_ready):
                 return
             acc = int(x.grad_ready)
-            bnm, uses = x.meta.get("bn"), x.meta.get("uses", 0)
-            done = (uses == 1 and not acc) or (self.fuse_bn_backward_last and uses > 1 and x.grad_writes == uses - 1 and acc)
-            ntl = int(self.lib.stp_maxpool3x3s2_bwd_bn_tiles(self.N, x.H, x.W, x.C, self.cdt)) if (
-                self.fuse_bn_backward and bnm is not None and done and self.slot_arena is None
-                and os.environ.get("STP_FUSE_POOL_BN", "0") == "1") else 0   # measured: 10.06 -> 10.14 ms when on (the gather + x read +
-            #                                                                    reduce in one kernel runs at half the rate of the pair)
-            if ntl > 0:
-                # the pool gradient completes dY of a BatchNormalization output (bn0: the other consumer is a decoder skip)
-                st = self._alloc((2 * x.C * ntl,), torch.float32)
-                self._emit(self.bwd, "stp_maxpool3x3s2_bwd_bn", idx.data_ptr(), out.grad.data_ptr(), self._gradbuf(x).data_ptr(), self.N,
-                           x.H, x.W, x.C, self.cdt, acc, bnm[0], bnm[1], bnm[2], bnm[3], bnm[4], bnm[5], st.data_ptr())
-                x.meta["bnb"] = (st, ntl)
-            else:
-                self._emit(self.bwd, "stp_maxpool3x3s2_bwd", idx.data_ptr(), out.grad.data_ptr(), self._gradbuf(x).data_ptr(), self.N,
-                           x.H, x.W, x.C, self.cdt, acc)
+            # the pool gradient completes dY of a BatchNormalization output (bn0: the other consumer is a decoder skip): OPT-IN -
+            # measured: 10.06 -> 10.14 ms when on (the gather + x read + reduce in one kernel runs at half the rate of the pair)
+            self._emit_grad_pass("stp_maxpool3x3s2_bwd", x, acc, (self.N, x.H, x.W, x.C, self.cdt),
+                                 (idx.data_ptr(), out.grad.data_ptr(), self._gradbuf(x).data_ptr(), self.N, x.H, x.W, x.C, self.cdt, acc),
+                                 os.environ.get("STP_FUSE_POOL_BN", "0") == "1")
             x.grad_ready = True
 
         if self.training:
@@ -1982,3 +1570,473 @@ class Plan(object):
         for info in self.params.values():
             if not info.trainable:
                 self.mask[info.offset:info.offset + info.numel] = 0
+
+
+class Dgrad(object):
+    """What ConvLayer's data-gradient chooser settled on: the launch parameters ``q`` and what the chosen form did with the layer."""
+
+    def __init__(self, q, layer, s2d=False, fold1=False, folded_up=False, two_dest=False, collapsed=False):
+        self.q, self.s2d, self.fold1, self.folded_up, self.two_dest = q, s2d, fold1, folded_up, two_dest
+        # (the class-collapsed form leaves the skip's gradient to a launch of its own: this one serves the first C0 channels only)
+        self.C1 = 0 if collapsed else layer.C1
+        self.flops = layer.flops * (layer.C0 - 0.0) / (layer.C0 + layer.C1) if collapsed else layer.flops
+
+
+# The plan of ONE convolution - one Plan.conv call, which documents the arguments: the layer's geometry and operands as attributes, one
+# method per planning step.  The constructor and `declare` run in both passes of Plan.define, `forward` in the real pass, `backward` from
+# the tape, in backward order.  Order is behaviour here: _gptr calls feed bwd_marks, _gradbuf calls may issue the pending weight-gradient
+# group or a join, so every call stays at its point of the launch list.
+class ConvLayer(object):
+
+    def __init__(self, plan, name, x, Cout, k, stride, pad, src1, upsample, residual, transpose, relu, same_tf, fold_shortcut, param_cols):
+        """Validates the operands; derives padding, the virtual input size (Hv, Wv), the output size and the channel counts."""
+        if transpose:
+            if stride != 1 or upsample or src1 is not None or residual is not None or k % 2:
+                raise StpShapeError("transpose=True is the plain stride-2 'same' Conv2DTranspose with an even kernel")
+            pad = k - 1 - (k // 2 - 1)
+        real_c0 = x.meta.get("real_c", x.C)
+        stem = real_c0 != x.C
+        if stem and (src1 is not None or upsample):
+            raise StpShapeError("padded-channel input supports a plain conv only")
+        C0, C1 = x.C, (src1.C if src1 is not None else 0)
+        if not stem and (C0 % plan.vec or C1 % plan.vec):
+            raise StpShapeError("%s: input channels (%d,%d) must be multiples of %d for dtype %s" % (name, C0, C1, plan.vec, plan.dtype))
+        Hv, Wv = (2 * x.H, 2 * x.W) if upsample else ((2 * x.H - 1, 2 * x.W - 1) if transpose else (x.H, x.W))
+        if src1 is not None and (src1.H, src1.W) != (Hv, Wv):
+            raise StpShapeError("%s: skip tensor is %dx%d, expected %dx%d" % (name, src1.H, src1.W, Hv, Wv))
+        Ho, Wo = (Hv + 2 * pad - k) // stride + 1, (Wv + 2 * pad - k) // stride + 1
+        if same_tf:
+            # TF / Keras padding='same': ceil(size / stride) outputs, the odd padding pixel goes to the bottom / right.  The
+            # kernels take the top/left padding and the output size; taps past the far edge are out of bounds = zero.
+            Ho, Wo = -(-Hv // stride), -(-Wv // stride)
+            pad = max((Ho - 1) * stride + k - Hv, 0) // 2
+            if max((Wo - 1) * stride + k - Wv, 0) // 2 != pad:
+                raise StpShapeError("%s: 'same' padding differs between height and width" % name)
+        self.KWp = k + (k & 1) if (stem and x.C == 4) else k      # 4 padded channels: one 16-byte vector = two horizontally adjacent taps
+        self.plan, self.name, self.x, self.src1, self.residual, self.fs, self.param_cols = plan, name, x, src1, residual, fold_shortcut, param_cols
+        self.Cout, self.k, self.stride, self.pad, self.upsample, self.transpose, self.relu = Cout, k, stride, pad, upsample, transpose, relu
+        self.real_c0, self.stem, self.C0, self.C1, self.Hv, self.Wv, self.Ho, self.Wo = real_c0, stem, C0, C1, Hv, Wv, Ho, Wo
+        self.Cin_master, self.Cinp = real_c0 + C1, C0 + C1
+        self.src_mode = ops.SRC_NEAREST2X if upsample else (ops.SRC_ZEROINS2X if transpose else ops.SRC_DIRECT)
+
+    def declare(self, param_name, param_shape, cout_pad, bias):
+        """Parameters, the output tensor, and what the dry pass sizes: the weight-gradient and bias-gradient workspaces."""
+        pl, name, x, src1, residual, Cout, k, Cin_master, param_cols = self.plan, self.name, self.x, self.src1, self.residual, self.Cout, self.k, self.Cin_master, self.param_cols
+        # (param_name / param_shape: conv3x3_taps - the 1x1 launch over the bytes of a 3x3 kernel registered under the layer's own name)
+        if param_cols is not None:
+            if k != 1 or self.stem or self.transpose or self.C1 or Cout % pl.vec or Cin_master % 4 or param_cols[0] % 4 or param_cols[1] % 4 \
+                    or param_cols[0] + Cin_master > param_cols[1]:
+                raise StpShapeError("%s: a column range of a shared kernel serves a plain 1x1 convolution with aligned channel counts" % name)
+            param_shape = None
+        w = pl.param((param_name or name) + "/kernel", (Cout, 1, 1, param_cols[1]) if param_cols is not None else (param_shape or (Cout, k, k, Cin_master)),
+                     "tkernel" if self.transpose else "kernel")
+        if param_shape is not None and int(np.prod(param_shape)) != Cout * k * k * Cin_master:
+            raise StpShapeError("%s: parameter view of %s does not match %d x %d x %d x %d" % (name, param_shape, Cout, k, k, Cin_master))
+        self.w, self.b = w, (pl.param(name + "/bias", (Cout,), "bias") if bias else None)
+        CoutB = self.CoutB = _rup(Cout, cout_pad or pl.vec)      # channels of the gradient buffer = K of the data gradient (cout_pad: conv3x3_taps)
+        self.x_ng, self.s_ng = x.needs_grad, (src1.needs_grad if src1 is not None else False)
+        self.out = pl._new(name, self.Ho, self.Wo, Cout, self.x_ng or self.s_ng or w.trainable or (residual is not None and residual.needs_grad))
+        self.out.gradC = CoutB
+        if bias:
+            pl._bn_ws_c = max(pl._bn_ws_c, CoutB)      # the bias gradient (stp_channel_sum) shares the BN workspace
+        pl._use(x, src1, residual)
+        # workspace sizing needs the wgrad plan: query the library (cheap, host only)
+        wp = self.wp = _lib.WgradParams()
+        wp.N, wp.Hs0, wp.Ws0, wp.Hv, wp.Wv, wp.C0, wp.C1, wp.src0_mode = pl.N, x.H, x.W, self.Hv, self.Wv, self.C0, self.C1, self.src_mode
+        wp.KH, wp.KW, wp.stride, wp.pad, wp.Ho, wp.Wo, wp.Cout = k, self.KWp, self.stride, self.pad, self.Ho, self.Wo, CoutB
+        wp.accumulate, wp.dtype, wp.splits = 0, pl.cdt, 0
+        if pl.training and w.trainable:
+            pl._wg_ws_bytes = max(pl._wg_ws_bytes, int(pl.lib.stp_conv2d_wgrad_workspace_bytes(C.byref(wp))))
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, bn_stats, flops_as):
+        """Weight copies, the launch parameters with their epilogue (bias, ReLU, statistics), the launch."""
+        pl, x, src1, residual, out, k, Cout = self.plan, self.x, self.src1, self.residual, self.out, self.k, self.Cout
+        self._weight_copies()
+        p = self.p = ops.conv_params(x.buf, self.wf, out.buf, N=pl.N, Hs0=x.H, Ws0=x.W, Hv=self.Hv, Wv=self.Wv, C0=self.C0, C1=self.C1,
+                                     src1=src1.buf if src1 is not None else None,
+                                     mode=self.src_mode, KH=k, KW=self.KWp, stride=self.stride, pad=self.pad,
+                                     Ho=self.Ho, Wo=self.Wo, Cout=Cout, dtype=pl.cdt, residual=residual.buf if residual is not None else None)
+        self._collapsed_copies()
+        self._register_bn_consumer()
+        if self.b is not None:
+            p.bias = pl._pptr(self.b)
+        if self.relu:
+            if self.CoutB != Cout:
+                raise StpShapeError("%s: a fused ReLU needs Cout to be a multiple of %d" % (self.name, pl.vec))
+            p.relu = 1        # Conv2D(activation='relu'): fused into the epilogue; its gradient masks dY first (stp_relu_bwd)
+        if bn_stats and pl.training and pl.slot_arena is not None and pl.N * self.Ho * self.Wo <= pl.bn_slots_max_rows:
+            p.stats_partial, p.stats_slots = out.meta["stats_slots"] = pl._slots(Cout)
+        elif bn_stats and pl.training:
+            # the BatchNormalization that follows takes its batch statistics from this conv's epilogue
+            nfl = int(pl.lib.stp_conv2d_stats_floats(C.byref(p)))
+            st = pl._alloc((max(nfl, 4),), torch.float32)
+            p.stats_partial = st.data_ptr()
+            out.meta["stats_table"] = pl._group_stats(p, st, Cout)       # (table, columns) the BatchNormalization reads
+        # algorithmic work of this layer: 2 * pixels * Cout * KH*KW*Cin with the REAL (unpadded) dims
+        self.flops = 2.0 * pl.N * self.Ho * self.Wo * Cout * k * k * self.Cin_master / (4.0 if self.transpose else 1.0)   # zero-inserted taps are not work
+        if flops_as is not None:
+            # (a launch of a RESTRUCTURED reference layer - the PSPNet head without its concatenation: the roofline bookkeeping keeps
+            #  counting the reference graph's convolution, SURVEY 8d's convention, not the cheaper form that is executed)
+            self.flops = float(flops_as)
+        pl._emit_conv(pl.fwd, p, {"layer": self.name, "pass": "fwd", "flops": self.flops, "tile": int(pl.lib.stp_conv2d_tile_for(C.byref(p))),
+                                  "src2": bool(self.C1 or self.upsample)})
+
+    def _weight_copies(self):
+        """The forward and data-gradient compute copies of the kernel, rebuilt from the fp32 master once per step."""
+        pl, w, Cout, k, KWp, Cinp, Cin_master, param_cols = self.plan, self.w, self.Cout, self.k, self.KWp, self.Cinp, self.Cin_master, self.param_cols
+        wf = self.wf = pl._alloc((_rup(Cout, 16) * k * KWp * Cinp,))
+        self.need_dgrad = pl.training and (self.x_ng or self.s_ng) and not self.stem
+        wb = self.wb = pl._alloc((_rup(Cinp, 16) * k * k * self.CoutB,)) if self.need_dgrad else None
+        self.out.meta["wb"] = wb
+        wsrc = pl._pptr(w)
+        if param_cols is not None:
+            w.pending_slices += 1      # (backward: the LAST range written makes the parameter's gradient final)
+            # the column range as a dense [Cout][Cin] fp32 matrix, refreshed every step in front of the batched weight preparation
+            wm = pl._alloc((Cout * Cin_master,), torch.float32)
+            pl._emit(pl.prep, "stp_copy_cols_f32", wm.data_ptr(), Cin_master, wsrc + 4 * int(param_cols[0]), int(param_cols[1]), Cout, Cin_master, 0)
+            wsrc = wm.data_ptr()
+        self.out.meta["w_master"] = (wsrc, Cout, Cin_master, k)      # (the space-to-depth data gradient builds its weights from the masters)
+        # collected here, issued as ONE batched launch per step (see _finish_prep)
+        pl._prep_layers.append((wsrc, wf.data_ptr(), wb.data_ptr() if wb is not None else None, Cout, k, k, Cin_master, KWp, Cinp, self.CoutB))
+
+    def _collapsed_copies(self):
+        """The class-collapsed weight copies of a convolution over upsample + concat, where its kernel takes them."""
+        pl, p, C0, C1, rows_f = self.plan, self.p, self.C0, self.C1, _rup(self.Cout, 16)
+        self.w4 = None
+        if not (self.upsample and self.src1 is not None and self.k == 3 and self.KWp == 3 and self.stride == 1 and self.pad == 1
+                and self.Cinp == self.Cin_master == C0 + C1
+                and os.environ.get("STP_UPCOLLAPSE", "1") != "0" and not pl.lib.stp_conv2d_scn_eligible(C.byref(p))
+                and int(pl.lib.stp_conv2d_halo_variant(C.byref(p))) < 0):
+            # (the narrow-output kernel - 64 + 64 -> 32 channels - keeps both halos in LDS and takes the plain weight copy; so does the
+            #  two-source form of the halo kernel, round 5: 128+ output channels)
+            return
+        # decoder conv1 = conv3x3(concat(UpSampling2D(2)(x), skip)): per output parity class the taps over the upsampled half read
+        # 2 x 2 low-resolution pixels - the forward multiplies them by class-summed weights (4 x C0 + 9 x C1 K columns instead
+        # of 9 x (C0 + C1)); the summed copy is rebuilt from the fp32 master with the other weight copies, once per step
+        wup = pl._alloc((rows_f * 16 * C0,))
+        pl._upc_layers.append((pl._pptr(self.w), wup.data_ptr(), self.Cout, rows_f, C0, C0 + C1))     # one batched launch (_finish_prep)
+        p.weight_up = wup.data_ptr()
+        if self.need_dgrad and self.x_ng and C0 % 16 == 0 and os.environ.get("STP_UPCOLLAPSE_BWD", "0") == "1":
+            # ... and the data gradient w.r.t. x is a 4x4 / stride-2 convolution of dY with the row / column tap sums.  OPT-IN:
+            # measured slower with today's kernels for the two resulting shapes (DESIGN.md), kept for the next round
+            self.w4 = pl._alloc((C0 * 16 * self.CoutB,))
+            pl._upc4_layers.append((pl._pptr(self.w), self.w4.data_ptr(), self.Cout, self.CoutB, C0, C0 + C1))
+
+    def _register_bn_consumer(self):
+        """Tells the BatchNormalization that produces ``x`` that this launch can normalise ``x`` itself (_fuse_bn_into_consumers)."""
+        pl, x, p, wp, w = self.plan, self.x, self.p, self.wp, self.w
+        if not pl.training or x.meta.get("apply_rec") is None or self.src1 is not None or self.transpose or self.stem:
+            return
+        if self.residual is None and pl.lib.stp_conv2d_sc_eligible(C.byref(p)) and (not w.trainable or pl.lib.stp_wgrad_sc_eligible(C.byref(wp))):
+            x.meta["sc_consumers"].append((p, wp))
+        elif pl.fuse_bn_halo and not self.upsample and pl.lib.stp_conv2d_halo_variant(C.byref(p)) >= 0:
+            # (p, wp, can the weight gradient normalise its operand itself: row-of-taps kernel - or no weight gradient at all)
+            x.meta["halo_consumers"].append((p, wp, (not w.trainable) or int(pl.lib.stp_conv2d_wgrad_kernel_id(C.byref(wp))) in (2, 3)))
+
+    # ------------------------------------------------------------------ backward
+    def backward(self):
+        """Backward entry (ReLU mask, lag-1 join, residual gradient), then the weight, bias and data gradients."""
+        pl, out, residual, b = self.plan, self.out, self.residual, self.b
+        if not out.needs_grad or not out.grad_ready:
+            return
+        dy = self.dy = out.grad
+        if self.relu:
+            pl._before_inplace_write(dy)
+            pl._emit(pl.bwd, "stp_relu_bwd", out.buf.data_ptr(), dy.data_ptr(), out.rows * out.gradC, pl.cdt)
+        # lag-1 join: the previous convolution's weight-gradient chain finishes before this layer's kernels start.
+        # (Letting the side chain fall further behind - joining only on a buffer hazard, see _gradbuf - measured
+        # SLOWER, 11.15 vs 10.88 ms/step: the chain then reads dY / x long after the main chain left them in L2.)
+        if pl._side_lag_join or not pl._side_groups_only:
+            pl._join_side()
+        # residual branch: d(residual) = dY
+        if residual is not None and residual.needs_grad:
+            if not residual.grad_ready and residual.gradC == out.gradC:
+                residual.grad = dy          # alias: dY is dead once this layer's backward has been issued
+                residual.grad_ready = True
+            else:
+                pl._emit(pl.bwd, "stp_add_inplace", pl._gradbuf(residual).data_ptr(), dy.data_ptr(), out.rows * out.gradC, pl.cdt)
+        if self.w.trainable:
+            self._weight_grad()
+        if b is not None and b.trainable and out.meta.get("loss_bias_grad") and self.Cout == 1:
+            # the 1-class head: the loss gradient kernel left the per-workgroup sums of dL/dlogit in its workspace
+            pl._emit(pl.bwd, "stp_sigmoid_loss_bias_grad", pl.ws_loss.data_ptr(), out.rows, pl._gptr(b), 0)
+        elif b is not None and b.trainable and out.meta.get("loss_bias_grad") == "multilabel":
+            # the multi-label head: one partial sum per class and gradient workgroup, left by stp_sigmoid_multilabel_loss
+            pl._emit(pl.bwd, "stp_sigmoid_multilabel_bias_grad", pl.ws_loss.data_ptr(), out.rows, self.Cout, pl._gptr(b), 0)
+        elif b is not None and b.trainable:
+            pl._emit_bias_grad(dy, out.rows, self.CoutB, self.Cout, b)
+        if self.need_dgrad and not out.meta.get("dgrad_folded"):
+            # (folded: a projection shortcut whose data gradient rode in its sibling's launch - fold_shortcut: nothing to issue)
+            self._data_grad()
+
+    # weight gradient: on the side stream, forked here (dY is final); joined before any kernel rewrites dY (_gradbuf)
+    # and at the end of the launch list
+    def _weight_grad(self):
+        """Destination (the arena, or a padded / column-range matrix), the launch - grouped or alone - and the copy back from such a matrix."""
+        pl, x, src1, w, wp, k, Cout, Cin_master, param_cols = self.plan, self.x, self.src1, self.w, self.wp, self.k, self.Cout, self.Cin_master, self.param_cols
+        padded, gcols = self.stem or self.CoutB != Cout, None
+        if padded:
+            dwp = pl._alloc((self.CoutB * k * self.KWp * self.Cinp,), torch.float32)
+            wp.dw = dwp.data_ptr()
+        elif param_cols is not None:
+            gcols = pl._alloc((Cout * Cin_master,), torch.float32)       # dense gradient of the column range, copied back below
+            wp.dw = gcols.data_ptr()
+        else:
+            wp.dw = pl._gptr(w)
+        wp.src0, wp.src1, wp.dy = x.meta.get("src_override") or x.buf.data_ptr(), (src1.buf.data_ptr() if src1 is not None else None), self.dy.data_ptr()
+        cls = int(pl.lib.stp_wgrad_group_class(C.byref(wp))) if (pl.wgrad_group_gflop > 0 and not padded and gcols is None) else 0
+        if cls:
+            self._wgrad_join_group(cls)
+        else:
+            # a layer outside the groups (stride 2, 1x1, stem, small-channel): the pending group is issued first, so a group
+            # = consecutive row-of-taps layers (a network stage) and the gradient arena stays final above the last visited layer
+            pl._flush_wgroup()
+            # (reads: see _gradbuf - dY is the only buffer of the chain that is ever rewritten; a padded dW is unpadded right below)
+            pl._emit_wgrad(wp, self.name, self.flops, {self.dy.data_ptr()}, defer_hi=0 if (padded or gcols is not None) else w.end)
+        if gcols is not None:
+            # (the arena range of the shared kernel is reported final - _gptr, bwd_marks - by the last of its ranges only)
+            w.pending_slices -= 1
+            gbase = pl._gptr(w) if w.pending_slices == 0 else pl.G.data_ptr() + 4 * w.offset
+            pl._emit_side(pl.bwd, "stp_copy_cols_f32", gbase + 4 * int(param_cols[0]), int(param_cols[1]), gcols.data_ptr(), Cin_master, Cout, Cin_master, 0)
+        if padded:
+            pl._emit_side(pl.bwd, "stp_weight_grad_unpad", dwp.data_ptr(), pl._gptr(w), Cout, k, k, Cin_master, self.KWp, self.Cinp, 0)
+        beta = x.meta.get("input_bn_beta")
+        if self.stem and beta is not None and beta.trainable:
+            pl._emit_side(pl.bwd, "stp_stem_beta_grad", dwp.data_ptr(), pl._pptr(w), pl._gptr(beta), Cout, k, k, self.real_c0, self.KWp, self.Cinp, self.real_c0)
+
+    # row-of-taps layer: joins the pending group (one launch per stage instead of one per layer); dY stays untouched
+    # until the group is issued (_gradbuf / the BatchNormalization backward's out-of-place accumulate see to that)
+    def _wgrad_join_group(self, cls):
+        pl = self.plan
+        if pl._wgroup and pl._wgroup_cls != cls:
+            pl._flush_wgroup()
+        pl._wgroup.append((self.wp, self.name, self.flops))
+        pl._wgroup_cls = cls
+        pl._wgroup_flops += self.flops
+        pl._wgroup_hi = max(pl._wgroup_hi, self.w.end)
+        pl._wgroup_reads.add(self.dy.data_ptr())
+        if pl._wgroup_flops >= pl.wgrad_group_gflop * 1e9:
+            pl._flush_wgroup()
+
+    # ------------------------------------------------------------------ data gradient
+    # The chooser.  The forms in the order they are tried - the first that takes the layer wins; a form that declines has issued nothing
+    # and leaves the plain launch parameters `q` untouched (a candidate is built, the library is asked, and it is adopted only on a yes):
+    #   scatter      1x1 / stride 2: low-resolution GEMM + scatter pass (issues its own launches: nothing else follows)
+    #   s2d          3x3 / stride 2 on the halo kernel, space-to-depth; the sibling shortcut's dY rides as a second source
+    #   parity fold  3x3 / stride 2, zero-inserted: the sibling shortcut's dY as one more tap of the (even, even) class
+    #   fold1        3x3 / stride 1 on the halo kernel: the sibling 1x1 / stride-1 shortcut's dY as a second source
+    #   collapsed    conv(concat(up(x), skip)) with STP_UPCOLLAPSE_BWD=1: 4x4 / stride-2 launch for x, a launch of its own for the skip
+    #   sum2x2       conv(up(x)) / conv(concat(up(x), skip)): the 2x2 sums of UpSampling2D's gradient in the epilogue of the small-channel
+    #                / wide-output kernel, else of the halo kernel (there only with the fused BatchNormalization backward)
+    #   plain        `q` as it is (an upsampled source then gets its gradient from the trailing stp_upsample2x_bwd pass)
+    # Then: the BatchNormalization-backward sums where this launch completes that gradient, the launch, the trailing pass.
+    def _data_grad(self):
+        pl, x = self.plan, self.x
+        self._dgrad_dests()
+        q = self._dgrad_plain()
+        if self.stride not in (1, 2):
+            raise StpShapeError("data gradient supports stride 1 and 2")
+        if self._form_scatter():
+            return
+        form = (self._form_s2d() or self._form_parity_fold(q) or self._form_fold1(q) or self._form_collapsed()
+                or self._form_sum2x2_stream(q) or self._form_sum2x2_halo(q) or Dgrad(q, self))
+        if form.folded_up and self.d0_hires is not None:
+            # the full-resolution gradient of the upsampled tensor is never written: give its buffer back (33-134 MB per decoder
+            # stage at batch 16, 512 x 512 - it used to stay allocated for the life of the plan)
+            pl._keep = [t for t in pl._keep if t is not self.d0_hires]
+            self.d0 = self.d0_hires = None
+        self._attach_bn_sums(form)
+        pl._emit_conv(pl.bwd, form.q, {"layer": self.name, "pass": "dgrad", "flops": form.flops,
+                                       "tile": int(pl.lib.stp_conv2d_tile_for(C.byref(form.q))), "s2d": form.s2d, "fold1": form.fold1})
+        if self.upsample and self.x_ng and not form.folded_up:
+            # the un-folded gradient of UpSampling2D as a pass of its own; where it completes dY of a BatchNormalization output: mask +
+            # backward sums in the same pass
+            acc = int(x.grad_ready)
+            pl._emit_grad_pass("stp_upsample2x_bwd", x, acc, (pl.N, x.H, x.W, self.C0, self.C0, pl.cdt),
+                               (self.d0.data_ptr(), pl._gradbuf(x).data_ptr(), pl.N, x.H, x.W, self.C0, self.C0, pl.cdt, acc),
+                               os.environ.get("STP_FUSE_UP_BN", "1") != "0")
+        if self.x_ng:
+            x.grad_ready = True
+        if self.s_ng:
+            self.src1.grad_ready = True
+
+    def _dgrad_dests(self):
+        """Destinations (d0, d1) and accumulate flags of the data gradient; an upsampled source gets a full-resolution buffer first."""
+        pl, x, src1, shape = self.plan, self.x, self.src1, (self.plan.N, self.Hv, self.Wv)
+        self.d0_hires = None
+        if self.upsample:
+            d0 = self.d0_hires = pl._alloc(shape + (self.C0,)) if self.x_ng else None      # released when the launch folds the 2 x 2 sums
+            self.acc0 = 0
+        else:
+            d0 = pl._gradbuf(x) if self.x_ng else None
+            self.acc0 = int(x.grad_ready)
+        d1 = pl._gradbuf(src1) if self.s_ng else None
+        self.acc1 = int(src1.grad_ready) if self.s_ng else 0
+        if d0 is None:
+            d0 = pl._alloc(shape + (self.C0,))      # gradient not wanted: scratch sink
+        if self.C1 and d1 is None:
+            d1 = pl._alloc(shape + (self.C1,))
+        self.d0, self.d1 = d0, d1
+
+    def _dgrad_plain(self):
+        """The plain form: a stride-1 convolution of (zero-inserted, for stride 2) dY with the flipped kernel copy ``wb``."""
+        pl, x, k, stride, Ho, Wo, C0 = self.plan, self.x, self.k, self.stride, self.Ho, self.Wo, self.C0
+        if self.transpose:
+            # gradient of the zero-inserted input at its even positions only = a plain stride-2 convolution of dY
+            return ops.conv_params(self.dy, self.wb, self.d0, N=pl.N, Hs0=Ho, Ws0=Wo, Hv=Ho, Wv=Wo, C0=self.CoutB, mode=ops.SRC_DIRECT, KH=k, KW=k,
+                                   stride=2, pad=k - 1 - self.pad, Ho=x.H, Wo=x.W, Cout=C0, dtype=pl.cdt, accumulate0=self.acc0)
+        return ops.conv_params(self.dy, self.wb, self.d0, N=pl.N, Hs0=Ho, Ws0=Wo,
+                               Hv=(2 * Ho - 1 if stride == 2 else Ho), Wv=(2 * Wo - 1 if stride == 2 else Wo),
+                               C0=self.CoutB, mode=(ops.SRC_ZEROINS2X if stride == 2 else ops.SRC_DIRECT), KH=k, KW=k, stride=1,
+                               pad=k - 1 - self.pad, Ho=self.Hv, Wo=self.Wv, Cout=C0 + self.C1, dtype=pl.cdt, dst1=self.d1, Cd0=C0,
+                               accumulate0=self.acc0, accumulate1=self.acc1)
+
+    # 1x1 / stride 2 (the projection shortcut of a bottleneck ResNet's first unit): the zero-inserted form runs the GEMM
+    # over all four parity classes of the high-resolution grid (229 us for 256 <- 512 channels at 4 x 256 x 256).  Instead:
+    # t = W^T dY at LOW resolution (a plain 1x1 / stride-1 launch), then one pass that puts t at the even positions of the
+    # gradient - and, when that completes the gradient of a BatchNormalization output, masks it and reduces the sums
+    def _form_scatter(self):
+        pl, x, N, Ho, Wo, C0 = self.plan, self.x, self.plan.N, self.Ho, self.Wo, self.C0
+        if not (self.stride == 2 and self.k == 1 and self.pad == 0 and not self.transpose and not self.upsample and self.src1 is None and self.x_ng
+                and self.fs is None and C0 % 4 == 0 and os.environ.get("STP_SCATTER_1X1S2", "1") != "0"):
+            return False
+        t_low = pl._alloc((N, Ho, Wo, C0))
+        qg = ops.conv_params(self.dy, self.wb, t_low, N=N, Hs0=Ho, Ws0=Wo, Hv=Ho, Wv=Wo, C0=self.CoutB, mode=ops.SRC_DIRECT, KH=1, KW=1,
+                             stride=1, pad=0, Ho=Ho, Wo=Wo, Cout=C0, dtype=pl.cdt)
+        pl._emit_conv(pl.bwd, qg, {"layer": self.name, "pass": "dgrad", "flops": 2.0 * N * Ho * Wo * self.Cout * self.Cin_master,
+                                   "tile": int(pl.lib.stp_conv2d_tile_for(C.byref(qg)))})
+        pl._emit_grad_pass("stp_scatter2x_bwd", x, self.acc0, (N, x.H, x.W, C0, pl.cdt),
+                           (t_low.data_ptr(), self.d0.data_ptr(), N, x.H, x.W, C0, pl.cdt, self.acc0))
+        x.grad_ready = True
+        return True
+
+    def _sibling_ready(self):
+        """The sibling projection shortcut (``fold_shortcut``) has its dY and its data-gradient weights at this layer's output size."""
+        fs = self.fs
+        return (fs is not None and self.src1 is None and self.x_ng and not self.transpose and fs.needs_grad and fs.grad_ready
+                and fs.meta.get("wb") is not None and (fs.H, fs.W) == (self.Ho, self.Wo))
+
+    def _fold_sibling(self):
+        """The sibling's share of x's gradient arrives with this launch (read by the sole / last decision of _attach_bn_sums)."""
+        self.fs.meta["dgrad_folded"] = True
+        self.x.grad_writes += 1
+
+    # SPACE-TO-DEPTH form (round 5, stp_conv_params.s2d_dgrad): the four output parity classes as ONE dense 2 x 2-tap
+    # convolution of dY into 4 x C0 class-major channels on the halo kernel, stored depth-to-space; the sibling 1x1 /
+    # stride-2 shortcut's dY rides along as a second source (its weights live at class 0 / tap 0 only)
+    def _form_s2d(self):
+        pl, fs, dy, Ho, Wo, C0, CoutB = self.plan, self.fs, self.dy, self.Ho, self.Wo, self.C0, self.CoutB
+        if not (self.stride == 2 and self.k == 3 and self.pad == 1 and not self.transpose and self.src1 is None and self.x_ng and pl.dtype != "fp32"
+                and not self.stem and self.Cout == CoutB and C0 == self.Cin_master and (self.Hv, self.Wv) == (2 * Ho, 2 * Wo)
+                and os.environ.get("STP_S2D", "1") != "0"
+                and os.environ.get("STP_HALO", "1") != "0"):      # (stp_conv2d_halo_variant ignores the A/B switch; the dispatcher honours it)
+            return None
+        fold = self._sibling_ready() and fs.gradC == CoutB and fs.meta.get("w_master", (0, 0, 0, 0))[1:] == (self.Cout, C0, 1)
+        qs = ops.conv_params(dy, dy, self.d0, N=pl.N, Hs0=Ho, Ws0=Wo, Hv=Ho, Wv=Wo, C0=CoutB, C1=(CoutB if fold else 0),
+                             src1=(fs.grad if fold else None), mode=ops.SRC_DIRECT, KH=2, KW=2, stride=1, pad=0, Ho=Ho, Wo=Wo,
+                             Cout=4 * C0, dtype=pl.cdt, accumulate0=self.acc0)
+        qs.s2d_dgrad = 1
+        qs.weight = self.wb.data_ptr()                   # the ordinary data-gradient copies: the kernel addresses them per parity class
+        if fold:
+            qs.fold_weight = fs.meta["wb"].data_ptr()
+        if int(pl.lib.stp_conv2d_halo_variant(C.byref(qs))) < 0:
+            return None
+        if fold:
+            self._fold_sibling()
+        return Dgrad(qs, self, s2d=True)
+
+    # the shortcut's 1x1 / stride-2 data gradient = one more (centre) tap of this launch's (even, even) parity class
+    def _form_parity_fold(self, q):
+        fs = self.fs
+        if not (self.stride == 2 and self.k == 3 and self._sibling_ready() and fs.gradC == self.CoutB and int(self.plan.lib.stp_conv2d_fold_ok(C.byref(q)))):
+            return None
+        q.fold_src, q.fold_weight, q.fold_C = fs.grad.data_ptr(), fs.meta["wb"].data_ptr(), self.CoutB
+        self._fold_sibling()
+        return Dgrad(q, self)
+
+    # the sibling 1x1 / stride-1 shortcut (first unit of ResNet18 / 34's stage 1): its dY is a second source of this launch
+    # whose centre tap carries the shortcut's weights (conv_halo.hip, FOLD1) - no separate launch accumulates into dX
+    def _form_fold1(self, q):
+        pl, fs = self.plan, self.fs
+        if not (self.stride == 1 and self.k == 3 and self.pad == 1 and not self.upsample and self._sibling_ready()
+                and fs.meta.get("w_master", (0, 0, 0, 0))[2:] == (self.C0, 1) and pl.dtype != "fp32" and os.environ.get("STP_HALO", "1") != "0"):
+            return None
+        c = _lib.ConvParams.from_buffer_copy(q)
+        c.fold_src, c.fold_weight, c.fold_C = fs.grad.data_ptr(), fs.meta["wb"].data_ptr(), fs.gradC
+        if int(pl.lib.stp_conv2d_halo_variant(C.byref(c))) < 0:
+            return None
+        self._fold_sibling()
+        return Dgrad(c, self, fold1=True)
+
+    # conv3x3(concat(UpSampling2D(2)(x), skip)): the skip gradient is the plain 3x3 data gradient with the skip's rows
+    # of the flipped weight copy; the gradient of x is a 4x4 / stride-2 convolution of dY with the tap sums (w4) that
+    # lands on the low-resolution tensor directly - no high-resolution gradient, no stp_upsample2x_bwd
+    def _form_collapsed(self):
+        pl, x, dy, wb, k, Ho, Wo, C0, C1, CoutB = self.plan, self.x, self.dy, self.wb, self.k, self.Ho, self.Wo, self.C0, self.C1, self.CoutB
+        if self.w4 is None:
+            return None
+        if self.s_ng:
+            q1 = ops.conv_params(dy, wb, self.d1, N=pl.N, Hs0=Ho, Ws0=Wo, Hv=Ho, Wv=Wo, C0=CoutB, mode=ops.SRC_DIRECT, KH=k, KW=k,
+                                 stride=1, pad=k - 1 - self.pad, Ho=self.Hv, Wo=self.Wv, Cout=C1, dtype=pl.cdt, accumulate0=self.acc1)
+            q1.weight = wb.data_ptr() + C0 * k * k * CoutB * wb.element_size()
+            pl._emit_conv(pl.bwd, q1, {"layer": self.name, "pass": "dgrad", "flops": self.flops * C1 / float(C0 + C1),
+                                       "tile": int(pl.lib.stp_conv2d_tile_for(C.byref(q1)))})
+        q = ops.conv_params(dy, self.w4, pl._gradbuf(x), N=pl.N, Hs0=Ho, Ws0=Wo, Hv=Ho, Wv=Wo, C0=CoutB, mode=ops.SRC_DIRECT,
+                            KH=4, KW=4, stride=2, pad=1, Ho=x.H, Wo=x.W, Cout=C0, dtype=pl.cdt, accumulate0=int(x.grad_ready))
+        return Dgrad(q, self, folded_up=True, collapsed=True)
+
+    # the small-channel kernel sums each 2x2 block in its epilogue: the hi-res gradient of the upsampled
+    # tensor is never written and stp_upsample2x_bwd disappears
+    # ... and the wide-output kernel does the same for conv3x3(concat(UpSampling2D(2)(x), skip)): the first C0
+    # channels are summed into the low-resolution gradient, the skip's C1 channels stay at full resolution
+    def _form_sum2x2_stream(self, q):
+        pl, x = self.plan, self.x
+        if not (self.upsample and self.x_ng and pl.fold_upsample_grad):
+            return None
+        c = _lib.ConvParams.from_buffer_copy(q)
+        c.dst_sum2x2 = 1
+        if not (pl.lib.stp_conv2d_scw_eligible(C.byref(c)) if self.C1 else (pl.lib.stp_conv2d_sc_eligible(C.byref(c)) and self.C0 % 4 == 0)):
+            return None
+        c.dst0, c.accumulate0 = pl._gradbuf(x).data_ptr(), int(x.grad_ready)
+        return Dgrad(c, self, folded_up=True, two_dest=bool(self.C1))
+
+    # ... and the halo kernel (64+ channel decoder stages, round 4): its epilogue sums the 2 x 2 blocks of the channel
+    # tiles of the upsampled source and runs the fused BatchNormalization backward on the LOW-resolution result
+    # (EP 3) - only in that fused form, i.e. when this launch completes the gradient of a BatchNormalization output
+    # that nothing else reads.  With a skip (two destinations) its C1 channels stay at full resolution.
+    def _form_sum2x2_halo(self, q):
+        pl, x, bnm = self.plan, self.x, self.x.meta.get("bn")
+        if not (self.upsample and self.x_ng and pl.fold_upsample_grad
+                and pl.fuse_bn_backward and bnm is not None and x.meta.get("uses", 0) == 1 and not x.grad_ready
+                and pl.slot_arena is None and os.environ.get("STP_HALO_FOLD_UP", "1") != "0"
+                and os.environ.get("STP_HALO", "1") != "0"):      # (the dispatcher honours STP_HALO=0: plan and dispatcher agree)
+            return None
+        c = _lib.ConvParams.from_buffer_copy(q)
+        c.dst_sum2x2, c.dst0, c.accumulate0 = 1, pl._gradbuf(x).data_ptr(), 0
+        pl._set_bnb(c, bnm)
+        if int(pl.lib.stp_conv2d_halo_variant(C.byref(c))) < 0:
+            return None
+        return Dgrad(c, self, folded_up=True, two_dest=bool(self.C1))
+
+    # the only consumer, or the LAST of several (every other consumer has already written or accumulated its
+    # share, this data gradient accumulates on top): its epilogue sees the complete gradient of the BN output; this launch
+    # and a sibling folded into it may be the only two consumers: the gradient is complete as well (Plan._completes_grad)
+    def _attach_bn_sums(self, form):
+        pl, x, q, C0, bnm = self.plan, self.x, form.q, self.C0, self.x.meta.get("bn")
+        done = pl._completes_grad(x, q.accumulate0, promoted=form.fold1 or form.s2d, last_ok=not self.upsample)
+        if not (pl.fuse_bn_backward and bnm is not None and done and (form.folded_up or not self.upsample) and (form.C1 == 0 or form.two_dest)
+                and self.x_ng and C0 % 4 == 0):
+            return
+        pl._set_bnb(q, bnm)
+        if pl.slot_arena is not None and pl.N * self.Hv * self.Wv <= pl.bn_slots_max_rows and not form.two_dest:
+            # (the two-destination kernel has no slot form - stp_conv2d_scw_eligible was checked without them, and with
+            #  slots the launch would fall through to the generic kernel, which refuses dst_sum2x2: float partial sums there)
+            q.stats_partial, q.stats_slots = x.meta["bnb_slots"] = pl._slots(C0)
+        else:
+            nfl = int(pl.lib.stp_conv2d_stats_floats(C.byref(q)))
+            st = pl._alloc((max(nfl, 4),), torch.float32)
+            q.stats_partial = st.data_ptr()
+            gt, gcols = pl._group_stats(q, st, C0)
+            # (gt is not st: the pre-reduced table ([2][C0][columns / G]) and its column count)
+            x.meta["bnb"] = (st, q) if gt is st else (gt, gcols)

@@ -724,6 +724,26 @@ def test_stats_sizing_query_does_not_depend_on_the_table_pointer():
     assert seen.get(736, 0) > 0, seen
 
 
+def test_plan_dump_is_stable_and_sees_a_plan_change(monkeypatch):
+    """tests/_plan_dump.py - the canonical text two versions of the plan builder are compared by ("Plan.conv in steps"): the
+    same network defined twice in one process gives the same text although every buffer lives at another address, no address is left
+    unresolved, and a switch that changes a data-gradient form (STP_S2D=0: stage 2's stride-2 conv1 leaves the space-to-depth form)
+    changes the text.  Host logic only."""
+    import _plan_dump
+    monkeypatch.delenv("STP_S2D", raising=False)
+
+    def text():
+        plan = graph.Plan(16, "bf16", "cpu", training=True)
+        plan.define(lambda p: nets.unet_resnet(p, "resnet18", 256, 256))
+        return plan, _plan_dump.dump(plan)
+    (plan, a), (_, b) = text(), text()          # (both plans alive: their buffers cannot share addresses)
+    assert a == b and _plan_dump.records(a) == len(plan.prep) + len(plan.fwd) + len(plan.bwd)
+    assert "s2d=True" in a and "0x" not in a and not [w for w in a.replace(",", " ").split() if w.isdigit() and int(w) >= 1 << 40]
+    monkeypatch.setenv("STP_S2D", "0")
+    c = text()[1]
+    assert c != a and "s2d=True" not in c
+
+
 def test_bench_names_every_launch_of_the_headline_plan():
     """bench.py's instrumented pass maps every launch of the step to the kernel the library runs for it (kernel_key): a launch kind
     it does not know (a new tile id) must fail here, on CPU, not in the driver's bench run."""
