@@ -539,6 +539,20 @@ int stp_sigmoid_multilabel_bias_grad(const void* workspace, int64_t pixels, int3
 int stp_softmax_cce_dice(const void* logits, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc,
                          int32_t dtype, float w_cce, float w_dice, float* scalars, void* dlogits, int32_t dl_channels,
                          float grad_scale, void* workspace, size_t workspace_bytes, void* stream);
+/* The multi-class head with the rest of the loss registry (segmentation.py:15-22) but lovasz_loss: weights5 (HOST pointer) =
+ * {categorical_crossentropy, dice_loss, iou_loss, jaccard_loss, focal_loss}, every term the Keras / musket formula on p = softmax of the
+ * first `classes` (2..32) channels and the one-hot target (uint8 class index per pixel, clamped to classes - 1): iou_loss ONE soft
+ * coefficient over the [pixels, classes] tensor (smooth 1), jaccard_loss the per-pixel distance over the class axis (smooth 100) averaged
+ * over pixels, focal_loss (gamma 2, alpha 0.25) a mean over pixels * classes elements.  scalars (fp32[12]) in the layout of
+ * stp_sigmoid_loss_ex: [1] = categorical_crossentropy, [8] = the soft iou, [10] = jaccard_loss, [11] = focal_loss (0 when its weight is 0: the
+ * term's per-class logarithms are then not evaluated), the rest as
+ * stp_softmax_cce_dice.  dlogits [pixels][dl_channels] gets the classes gradients x grad_scale and exactly-zero padding (NULL: scalars
+ * only).  Deterministic (fixed-order reduction, no atomics).  STP_E_BADARG for classes outside 2..32, ldc < classes, dl_channels <
+ * classes or the other build's 16-bit dtype; STP_E_WORKSPACE below stp_loss_workspace_bytes().  Not here: lovasz_loss on several
+ * classes, a fused low-resolution (_up) form, a bias-gradient shortcut from workgroup sums. */
+int stp_softmax_loss_ex(const void* logits, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc,
+                        int32_t dtype, const float* weights5, float* scalars, void* dlogits, int32_t dl_channels,
+                        float grad_scale, void* workspace, size_t workspace_bytes, void* stream);
 /* The same loss on class logits the network produces at 1 / factor of the mask's resolution and resizes bilinearly (segmentation_models
  * 0.2.1: PSPNet `final_interpolation: bilinear` x downsample_factor, schemas/segmentation.raml:225-249; FPN's last UpSampling2D(4,
  * 'bilinear')) - replaces, in the training step, stp_resize_bilinear of the logits + stp_softmax_cce_dice + stp_scale_by_device +

@@ -155,6 +155,7 @@ SIGNATURES = {
     "stp_sigmoid_loss_bias_grad": (i32, [vp, i64, vp, i32, vp]),
     "stp_sigmoid_multilabel_loss": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, i32, f32, vp, sz, vp]),
     "stp_sigmoid_multilabel_bias_grad": (i32, [vp, i64, i32, vp, i32, vp]),
+    "stp_softmax_loss_ex": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, i32, f32, vp, sz, vp]),
     "stp_lovasz_workspace_bytes": (sz, [i64, i32]),
     "stp_lovasz_hinge": (i32, [vp, vp, i32, i64, i32, f32, vp, vp, i32, vp, sz, vp]),
     "stp_sigmoid": (i32, [vp, vp, i64, i32, vp]),

@@ -22,8 +22,9 @@ CAPTURE_MODE = "thread_local"
 SCALAR_NAMES = ("loss", "binary_crossentropy", "dice_loss", "dice", "binary_accuracy")
 
 
-EXTENDED_LOSSES = ("iou_loss", "jaccard_loss", "focal_loss", "lovasz_loss")      # sigmoid heads only (stp_sigmoid_loss_ex, stp_lovasz_hinge,
-                                                                                # stp_sigmoid_multilabel_loss: all but lovasz_loss)
+EXTENDED_LOSSES = ("iou_loss", "jaccard_loss", "focal_loss", "lovasz_loss")      # stp_sigmoid_loss_ex + stp_lovasz_hinge (one class);
+                                                                                # stp_sigmoid_multilabel_loss and stp_softmax_loss_ex (several
+                                                                                # classes): all but lovasz_loss
 MAX_MULTILABEL_CLASSES = 8          # one target byte per pixel: bit c = class c
 
 
@@ -35,12 +36,14 @@ def is_multilabel(classes, activation):
 def parse_loss(spec, classes=1, architecture=None, activation=None):
     """``"binary_crossentropy+0.1*dice_loss"`` -> (w_ce, w_dice) or, when the spec names one of the other registry entries
     of reference segmentation.py:15-22, (w_ce, w_dice, w_iou, w_jaccard, w_focal, w_lovasz)  (grammar: reference README.md:210-214).
+    Every head but DeepLabV3's takes them (several classes: the head has to be named - ``activation`` "sigmoid" or "softmax";
+    a call that leaves it out gets the two terms every multi-class head has); ``lovasz_loss`` needs the one-class head.
     The cross-entropy term is ``binary_crossentropy`` for the sigmoid heads (one class, or ``activation="sigmoid"`` with several:
     multi-label) and ``categorical_crossentropy`` for the softmax head (schemas/segmentation.raml:12-21)."""
     sigmoid = classes == 1 or is_multilabel(classes, activation)
     ce = "binary_crossentropy" if sigmoid else "categorical_crossentropy"
     w = {ce: 0.0, "dice_loss": 0.0}
-    if sigmoid and architecture != "DeepLabV3":
+    if (sigmoid or activation == "softmax") and architecture != "DeepLabV3":
         w.update((k, 0.0) for k in EXTENDED_LOSSES)
     for term in str(spec).split("+"):
         term = term.strip()
@@ -53,7 +56,8 @@ def parse_loss(spec, classes=1, architecture=None, activation=None):
             raise ValueError("loss %r is not available in the HIP backend (have: %s)" % (name, ", ".join(sorted(w))))
         w[name] += k
     if classes > 1 and w.get("lovasz_loss"):
-        raise ValueError("lovasz_loss is not available for a multi-label head (the HIP backend has the binary Lovasz hinge of one class)")
+        raise ValueError("lovasz_loss is not available for a multi-label head or a softmax head of several classes "
+                         "(the HIP backend has the binary Lovasz hinge of one class)")
     if any(w.get(k) for k in EXTENDED_LOSSES):
         return (w[ce], w["dice_loss"]) + tuple(w[k] for k in EXTENDED_LOSSES)
     return w[ce], w["dice_loss"]
@@ -91,6 +95,9 @@ class HipSegModel(object):
         # psp_conv_filters - schemas/segmentation.raml:179-249), passed to the network definition as keywords
         self.net_kwargs = dict(net_kwargs or {})
         self.loss_w = parse_loss(loss, classes, architecture, self.head_activation)
+        # terms the loss kernel does not evaluate, left out of metrics() and of the epoch log: stp_softmax_loss_ex skips focal_loss'
+        # per-class logarithms when the spec gives it no weight (its scalar slot is then 0, not the loss)
+        self.unevaluated_terms = ("focal_loss",) if (self.head_activation == "softmax" and len(self.loss_w) > 2 and not self.loss_w[4]) else ()
         self.optimizer = optimizer.lower()
         if self.optimizer not in ("adam", "sgd", "rmsprop", "nadam"):
             raise ValueError("optimizer %r is not available in the HIP backend (have: SGD, Adam, RMSprop, Nadam)" % optimizer)
@@ -538,8 +545,10 @@ class HipSegModel(object):
         out["iou"], out["iot"] = float(s[8]), float(s[9])
         if len(self.loss_w) > 2:
             out["iou_loss"], out["jaccard_loss"], out["focal_loss"] = 1.0 - float(s[8]), float(s[10]), float(s[11])
-            if not self.multilabel:
+            if self.classes == 1:
                 out["lovasz_loss"] = float(s[12])
+            for k in self.unevaluated_terms:
+                out.pop(k, None)
         return out
 
     def logits(self):

@@ -1,0 +1,315 @@
+// Multi-class softmax head with the whole loss registry but lovasz_loss: the weighted sum of categorical_crossentropy, dice_loss,
+// iou_loss, jaccard_loss and focal_loss (oracle/losses.py) on p = softmax(z) and the one-hot y of the target class t, classes = 2..32:
+//   categorical_crossentropy / dice_loss   exactly the forms of softmax_loss_partial_kernel / softmax_loss_grad_kernel (loss_optim.hip)
+//   iou_loss      1 - (I + 1) / U with I = sum p_t and U = pixels + sum p - I + 1: the sums the value pass takes anyway
+//   jaccard_loss  per pixel 100 (1 - a / b), a = p_t + 100, b = 101 + sum_c p_c - p_t, mean over pixels - no class loop
+//   focal_loss    gamma 2, alpha 0.25, q = clip(p, 1e-7, 1 - 1e-7): -0.25 (1 - q)^2 log q for c == t, -0.75 q^2 log(1 - q) otherwise, both
+//                 means over pixels * classes elements; the clip passes no gradient; one v_log_f32 per class in both passes (the oracle's
+//                 two constant cross terms, ~2.5e-22 per element, are left out as in loss_multilabel.hip)
+// through the softmax: dz_k = p_k (G_k - sum_c G_c p_c), G = the weighted sum of the d / dp.
+// Three launches as stp_softmax_cce_dice: value pass (one thread per pixel, the row in registers, 16 partial sums per workgroup, fixed
+// order, no atomics) -> one-workgroup finalize in double (12 scalars, the layout of stp_sigmoid_loss_ex) -> gradient pass.  The passes
+// are VALU-bound (see softmax_row.h), so the weights - launch-uniform - pick an INSTANCE: the focal class loops and the iou / jaccard
+// terms are compiled out when their weights are zero.
+#include "softmax_row.h"
+
+#define SMX_NSUM 16
+#define SMX_MAX_BLOCKS 1024          // value-pass workgroups (stp_loss_workspace_bytes covers 1024 x 16 floats)
+#define SMX_GRAD_MAX_BLOCKS 4096
+#define SMX_JACCARD_SMOOTH 100.f
+#define SMX_FOCAL_ALPHA 0.25f
+
+struct SmxWeights { float w[5]; };   // categorical_crossentropy, dice_loss, iou_loss, jaccard_loss, focal_loss
+
+// 1 - p_c without cancellation: at most one probability of a row exceeds 0.5 - for the largest one (index *imax) 1 - p is the sum of
+// the OTHERS (returned), for every other class 1 - p_c >= 0.5 is exact enough as written.  A confidently wrong pixel (a class that is not
+// the target at p -> 1) is where focal_loss is largest: log(1 - p) and 1 / (1 - p) of a rounded 1.f - p lose 1e-7 / (1 - p) there.
+template <int CM>
+__device__ __forceinline__ float smx_rest(const float (&p)[CM], int* imax) {
+  float pmax = p[0], rest = 0.f;
+  int im = 0;
+#pragma unroll
+  for (int c = 1; c < CM; ++c) {
+    const bool gt = p[c] > pmax;
+    pmax = gt ? p[c] : pmax;
+    im = gt ? c : im;
+  }
+#pragma unroll
+  for (int c = 0; c < CM; ++c) rest += c == im ? 0.f : p[c];                 // (p[c] = 0 beyond `classes`)
+  *imax = im;
+  return rest;
+}
+
+// value pass: per-workgroup partials of
+//   0 cce_pixel  1 p  2 y (= 1 per pixel)  3 p_t  4 [pmax>.5]  5 [p_t>.5]  6 count of th == y  7 jaccard_pixel  8 focal_e   (9..15 zero)
+template <typename T, int CM, bool FOCAL>
+__global__ __launch_bounds__(256) void smx_partial_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ target, int64_t pixels,
+                                                          int classes, int ldc, bool vec, bool vec4, float* __restrict__ partial) {
+  float a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int64_t per = (pixels + gridDim.x - 1) / gridDim.x;
+  const int64_t i0 = (int64_t)blockIdx.x * per, i1 = i0 + per < pixels ? i0 + per : pixels;
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+    float p[CM];
+    softmax_row<T, CM>(logits + i * ldc, classes, vec, p, vec4);
+    const int t = target[i] < classes ? target[i] : classes - 1;
+    // the per-class sums of the one-hot target in closed form, as softmax_loss_partial_kernel takes them
+    float pt = 0.f, pmax = 0.f, psum = 0.f;
+#pragma unroll
+    for (int c = 0; c < CM; ++c) {
+      pt = c == t ? p[c] : pt;
+      pmax = fmaxf(pmax, p[c]);                      // (p[c] = 0 beyond `classes`)
+      psum += p[c];
+    }
+    const float tt = pt > 0.5f ? 1.f : 0.f, tm = pmax > 0.5f ? 1.f : 0.f;
+    a[1] += psum;
+    a[2] += 1.f;
+    a[3] += pt;
+    a[4] += tm;
+    a[5] += tt;
+    a[6] += (float)classes - (pt > 0.5f ? 0.f : 1.f + tm);
+    a[0] += -__logf(fminf(fmaxf(pt, 1e-7f), 1.f - 1e-7f));
+    // jaccard: 1 - a / b = (b - a) / b with b - a = 1 + sum_c p_c - 2 p_t (no cancellation against the smooth term)
+    a[7] += SMX_JACCARD_SMOOTH * __fdividef(1.f + psum - 2.f * pt, SMX_JACCARD_SMOOTH + 1.f + psum - pt);
+    if constexpr (FOCAL) {
+      int imax;
+      const float rest = smx_rest(p, &imax);
+      float f = 0.f;
+#pragma unroll
+      for (int c = 0; c < CM; ++c) {
+        if (c < classes) {
+          const float q = fminf(fmaxf(p[c], 1e-7f), 1.f - 1e-7f);
+          const float omq = fminf(fmaxf(c == imax ? rest : 1.f - p[c], 1e-7f), 1.f - 1e-7f);      // 1 - q
+          f += c == t ? -SMX_FOCAL_ALPHA * omq * omq * __logf(q) : -(1.f - SMX_FOCAL_ALPHA) * q * q * __logf(omq);
+        }
+      }
+      a[8] += f;
+    }
+  }
+  __shared__ float red[4][9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) a[e] = wave_sum(a[e]);
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int e = 0; e < 9; ++e) red[threadIdx.x >> 6][e] = a[e];
+  __syncthreads();
+  if (threadIdx.x < SMX_NSUM)
+    partial[(size_t)blockIdx.x * SMX_NSUM + threadIdx.x] =
+        threadIdx.x < 9 ? red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x] : 0.f;
+}
+
+// the 12 scalars of stp_sigmoid_loss_ex: 0 loss 1 categorical_crossentropy 2 dice_loss 3 dice 4 accuracy 5 sum_p 6 sum_y 7 sum_py 8 iou
+// 9 iot 10 jaccard_loss 11 focal_loss; 1..9 as softmax_loss_finalize_kernel defines them
+__global__ __launch_bounds__(256) void smx_finalize_kernel(const float* partial, int blocks, double inv_pixels, double inv_elems, SmxWeights lw,
+                                                           float* scalars) {
+  __shared__ double sh[16][SMX_NSUM];
+  const int e = threadIdx.x & 15, lane = threadIdx.x >> 4;
+  double a = 0.0;
+  {
+    int b = lane;
+    for (; b + 48 < blocks; b += 64) {        // four partials in flight (a run-time trip count keeps one); fixed order of additions
+      float v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = partial[(size_t)(b + 16 * u) * SMX_NSUM + e];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) a += (double)v[u];
+    }
+    for (; b < blocks; b += 16) a += (double)partial[(size_t)b * SMX_NSUM + e];
+  }
+  sh[lane][e] = a;
+  __syncthreads();
+  for (int w = 8; w > 0; w >>= 1) {
+    if (lane < w) sh[lane][e] += sh[lane + w][e];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const double* s = sh[0];
+  const double cce = s[0] * inv_pixels;
+  const double dice_l = 1.0 - (2.0 * s[3] + 1.0) / (s[2] + s[1] + 1.0);
+  const double iou = (s[3] + 1.0) / (s[2] + s[1] - s[3] + 1.0);
+  const double jac = s[7] * inv_pixels, focal = s[8] * inv_elems;
+  scalars[0] = (float)(lw.w[0] * cce + lw.w[1] * dice_l + lw.w[2] * (1.0 - iou) + lw.w[3] * jac + lw.w[4] * focal);
+  scalars[1] = (float)cce;
+  scalars[2] = (float)dice_l;
+  scalars[3] = (float)((2.0 * s[5] + 1.0) / (s[2] + s[4] + 1.0));
+  scalars[4] = (float)(s[6] * inv_elems);
+  scalars[5] = (float)s[1];
+  scalars[6] = (float)s[2];
+  scalars[7] = (float)s[3];
+  scalars[8] = (float)iou;
+  scalars[9] = (float)((s[5] + 1.0) / (s[2] + s[4] - s[5] + 1.0));
+  scalars[10] = (float)jac;
+  scalars[11] = (float)focal;
+}
+
+// gradient pass: dL/dlogit of the `classes` channels x grad_scale into [pixels][dlc], padding channels exactly 0.
+// EXT: iou_loss or jaccard_loss carries a weight; FOCAL: focal_loss does.
+template <typename T, int CM, bool EXT, bool FOCAL>
+__global__ __launch_bounds__(256) void smx_grad_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ target, int64_t pixels,
+                                                       int classes, int ldc, bool vec, bool vec4, const float* __restrict__ scalars,
+                                                       SmxWeights lw, float inv_pixels, float inv_elems, float grad_scale,
+                                                       T* __restrict__ dl, int dlc, bool vout) {
+  constexpr int V = Elem<T>::VEC;
+  const float w_cce = lw.w[0], w_dice = lw.w[1];
+  const float sp = scalars[5], sy = scalars[6], spy = scalars[7];
+  const float den = sy + sp + 1.f;
+  const float inv_den2 = 1.f / (den * den);
+  const float num = 2.f * spy + 1.f;
+  const float uden = sy + sp - spy + 1.f, unum = spy + 1.f;          // iou_coef = unum / uden
+  const float inv_uden2 = 1.f / (uden * uden);
+  // iou: d / dp_c = -(y_c U - (I + 1)(1 - y_c)) / U^2 -> one value for the target class, one for the others
+  const float iou1 = -lw.w[2] * uden * inv_uden2, iou0 = lw.w[2] * unum * inv_uden2;
+  const float wf = lw.w[4] * inv_elems;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pixels; i += (int64_t)gridDim.x * 256) {
+    float p[CM];
+    softmax_row<T, CM>(logits + i * ldc, classes, vec, p, vec4);
+    const int t = target[i] < classes ? target[i] : classes - 1;
+    float pt = 0.f;
+#pragma unroll
+    for (int c = 0; c < CM; ++c) pt = c == t ? p[c] : pt;
+    const bool inr = pt >= 1e-7f && pt <= 1.f - 1e-7f;   // the clip passes no gradient outside
+    // dice: G_c = d dice_loss / d p_c = -(2 y_c den - num) / den^2 ; dz_k = p_k (G_k - sum_c G_c p_c)
+    // sum_c G_c p_c with G_c = (num - 2 y_c den) / den^2: (num sum_c p_c - 2 den p_t) / den^2 - no loop over the classes
+    float psum = 0.f;
+#pragma unroll
+    for (int c = 0; c < CM; ++c) psum += p[c];                                                           // p[c] = 0 beyond classes
+    const float gp = (num * psum - 2.f * den * pt) * inv_den2;
+    float g[CM];
+    // iou and jaccard: E_c = d / dp_c = e1 for the target class, e0 for the rest, ge = sum_c E_c p_c
+    float e0 = 0.f, e1 = 0.f, ge = 0.f;
+    if constexpr (EXT) {
+      // jaccard: d / dp_c = -100 (y_c b - a (1 - y_c)) / b^2 / pixels
+      const float ja = pt + SMX_JACCARD_SMOOTH, jb = SMX_JACCARD_SMOOTH + 1.f + psum - pt;
+      const float jscale = lw.w[3] * SMX_JACCARD_SMOOTH * __builtin_amdgcn_rcpf(jb * jb) * inv_pixels;
+      e0 = iou0 + jscale * ja;
+      e1 = iou1 - jscale * jb;
+      ge = e0 * (psum - pt) + e1 * pt;
+    }
+    // focal: with F_c = d focal / dp_c, h_c = p_c F_c and H = sum_c h_c the logits get dz_k = h_k - p_k H.  For a class that is NOT the target
+    // F_c grows as 1 / (1 - p_c) and h_k - p_k H cancels to O(1) from terms of that size - so the largest class m (the only one that can
+    // have p > 0.5) is kept apart as u_m = h_m (1 - p_m), which has no division, and r = 1 - p_m (smx_rest):
+    //   dz_m = u_m - p_m Hrest,   dz_k = h_k - p_k Hrest - u_m (p_k / r) for k != m   (Hrest = sum over c != m of h_c; p_k <= r)
+    //   target:  h = 0.25 (2 p (1 - p) log p - (1 - p)^2)           others:  u = -0.75 (2 p^2 (1 - p) log(1 - p) - p^3), h = u / (1 - p)
+    int imax = 0;
+    float hrest = 0.f, umax = 0.f, rr = 0.f;
+    if constexpr (FOCAL) {
+      const float rest = smx_rest(p, &imax);
+      rr = __builtin_amdgcn_rcpf(fmaxf(rest, 1e-37f));
+#pragma unroll
+      for (int c = 0; c < CM; ++c) {
+        const float pr = p[c];
+        const float om = c == imax ? rest : 1.f - pr;
+        const bool in = pr >= 1e-7f && om >= 1e-7f;              // the clip to [eps, 1 - eps] passes no gradient (false beyond `classes`: p = 0)
+        const float lg = __logf(c == t ? pr : om);
+        const float w = (2.f * pr * om * lg - (c == t ? om * om : pr * pr)) * (c == t ? wf * SMX_FOCAL_ALPHA : -wf * (1.f - SMX_FOCAL_ALPHA));
+        // w = h for the target class, u / p for the others
+        const float h = c == t ? w : w * pr * __builtin_amdgcn_rcpf(om);
+        const float u = c == t ? w * om : w * pr;
+        g[c] = in && c != imax ? h : 0.f;
+        hrest += g[c];
+        umax = in && c == imax ? u : umax;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CM; ++c) {
+      const float y = c == t ? 1.f : 0.f;
+      float v = inr ? w_cce * (p[c] - y) * inv_pixels : 0.f;
+      v += w_dice * p[c] * ((-(2.f * y * den - num) * inv_den2) - gp);
+      if constexpr (EXT) v += p[c] * ((c == t ? e1 : e0) - ge);
+      if constexpr (FOCAL) v += c == imax ? umax - p[c] * hrest : g[c] - p[c] * hrest - umax * (p[c] * rr);
+      g[c] = c < classes ? v * grad_scale : 0.f;
+    }
+    T* o = dl + i * dlc;
+    if (vout) {
+#pragma unroll
+      for (int v = 0; v < 32 / V; ++v) {
+        if (v * V >= dlc) break;
+        u32x4 r = {0u, 0u, 0u, 0u};
+        auto gv = [&](int idx) { return idx < CM ? g[idx % CM] : 0.f; };      // channels past the class bucket are padding
+        if constexpr (sizeof(T) == 2) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) r[e] = pack_bf16x2(gv(v * V + 2 * e), gv(v * V + 2 * e + 1));
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) r[e] = __float_as_uint(gv(v * V + e));
+        }
+        *reinterpret_cast<u32x4*>(o + v * V) = r;
+      }
+      for (int c = 32; c < dlc; c += V) *reinterpret_cast<u32x4*>(o + c) = u32x4{0u, 0u, 0u, 0u};
+    } else {
+#pragma unroll
+      for (int c = 0; c < CM; ++c) if (c < classes) Elem<T>::store(o + c, g[c]);
+      for (int c = classes; c < dlc; ++c) Elem<T>::store(o + c, 0.f);
+    }
+  }
+}
+
+static int smx_value_blocks(int64_t pixels) {
+  const int64_t b = pixels / 1024;
+  return (int)(b < 1 ? 1 : b > SMX_MAX_BLOCKS ? SMX_MAX_BLOCKS : b);
+}
+static int smx_grad_blocks(int64_t pixels) {
+  const int64_t g = (pixels + 255) / 256;
+  return (int)(g > SMX_GRAD_MAX_BLOCKS ? SMX_GRAD_MAX_BLOCKS : g);
+}
+
+template <typename T, int CM>
+static void smx_launch(const T* logits, const uint8_t* target, int64_t pixels, int classes, int ldc, const SmxWeights& lw, float* scalars,
+                       T* dl, int dlc, float grad_scale, float* ws, hipStream_t s) {
+  constexpr int V = Elem<T>::VEC;
+  // the widest row access the stride and the base alignment allow: 16 bytes, 8 bytes (16-bit rows of 4 k elements), element by element
+  const uintptr_t base = reinterpret_cast<uintptr_t>(logits);
+  const bool vec = (ldc % V) == 0 && CM % V == 0 && (base & 15) == 0;
+  const bool vec4 = !vec && sizeof(T) == 2 && (ldc % 4) == 0 && (CM % 4) == 0 && (base & 7) == 0;
+  const bool focal = lw.w[4] != 0.f, ext = lw.w[2] != 0.f || lw.w[3] != 0.f;
+  const int blocks = smx_value_blocks(pixels);
+  const double inv_pixels = 1.0 / (double)pixels, inv_elems = 1.0 / ((double)pixels * classes);
+  if (focal)
+    hipLaunchKernelGGL((smx_partial_kernel<T, CM, true>), dim3(blocks), dim3(256), 0, s, logits, target, pixels, classes, ldc, vec, vec4, ws);
+  else
+    hipLaunchKernelGGL((smx_partial_kernel<T, CM, false>), dim3(blocks), dim3(256), 0, s, logits, target, pixels, classes, ldc, vec, vec4, ws);
+  hipLaunchKernelGGL(smx_finalize_kernel, dim3(1), dim3(256), 0, s, ws, blocks, inv_pixels, inv_elems, lw, scalars);
+  if (!dl) return;
+  const bool vout = (dlc % V) == 0 && (reinterpret_cast<uintptr_t>(dl) & 15) == 0;
+  const int g = smx_grad_blocks(pixels);
+#define SMX_GRAD(EXT, FOCAL)                                                                                                              \
+  hipLaunchKernelGGL((smx_grad_kernel<T, CM, EXT, FOCAL>), dim3(g), dim3(256), 0, s, logits, target, pixels, classes, ldc, vec, vec4, scalars, \
+                     lw, (float)inv_pixels, (float)inv_elems, grad_scale, dl, dlc, vout)
+  if (focal) {
+    if (ext) SMX_GRAD(true, true); else SMX_GRAD(false, true);
+  } else {
+    if (ext) SMX_GRAD(true, false); else SMX_GRAD(false, false);
+  }
+#undef SMX_GRAD
+}
+
+template <typename T>
+static void smx_dispatch(const T* logits, const uint8_t* target, int64_t pixels, int classes, int ldc, const SmxWeights& lw, float* scalars,
+                         T* dl, int dlc, float grad_scale, float* ws, hipStream_t s) {
+#define SMX_GO(CM) smx_launch<T, CM>(logits, target, pixels, classes, ldc, lw, scalars, dl, dlc, grad_scale, ws, s)
+  if (classes <= 4) SMX_GO(4);
+  else if (classes <= 8) SMX_GO(8);
+  else if (classes <= 16) SMX_GO(16);
+  else if (classes <= 24) SMX_GO(24);
+  else SMX_GO(32);
+#undef SMX_GO
+}
+
+extern "C" int stp_softmax_loss_ex(const void* logits, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype,
+                                   const float* weights5, float* scalars, void* dlogits, int32_t dl_channels, float grad_scale,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (!stp_dtype_ok(dtype)) return STP_E_BADARG;      // (the other build's 16-bit code, or garbage)
+  if (!logits || !target || !weights5 || !scalars || !workspace || pixels <= 0) return STP_E_BADARG;
+  if (classes < 2 || classes > STP_MAX_CLASSES || ldc < classes || dl_channels < classes) return STP_E_BADARG;
+  if (workspace_bytes < stp_loss_workspace_bytes()) return STP_E_WORKSPACE;
+  SmxWeights lw;
+  for (int i = 0; i < 5; ++i) lw.w[i] = weights5[i];
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == STP_H16)
+    smx_dispatch<bf16_t>((const bf16_t*)logits, target, pixels, classes, ldc, lw, scalars, (bf16_t*)dlogits, dl_channels, grad_scale,
+                         (float*)workspace, s);
+  else
+    smx_dispatch<float>((const float*)logits, target, pixels, classes, ldc, lw, scalars, (float*)dlogits, dl_channels, grad_scale,
+                        (float*)workspace, s);
+  STP_LAUNCH_CHECK();
+  return STP_OK;
+}

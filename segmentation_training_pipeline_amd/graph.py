@@ -1417,11 +1417,26 @@ class Plan(object):
         logits.meta["loss_bias_grad"] = "multilabel" if (self.training and self.dls is None) else False
         logits.grad_ready = self.training
 
-    def softmax_loss(self, logits, target, w_cce, w_dice):
-        """channel softmax + w_cce*categorical_crossentropy + w_dice*dice_loss (target = class index per pixel)."""
+    def softmax_loss(self, logits, target, w_cce, w_dice, w_iou=0.0, w_jaccard=0.0, w_focal=0.0):
+        """channel softmax + w_cce*categorical_crossentropy + w_dice*dice_loss [+ w*iou_loss + w*jaccard_loss + w*focal_loss on the
+        one-hot target: stp_softmax_loss_ex] (target = class index per pixel)."""
         if logits.C < 2:
             raise StpShapeError("categorical loss expects at least two classes")
         if self.dry:
+            return
+        if w_iou or w_jaccard or w_focal:
+            # one launch on the full-resolution logits: the extended loss has no low-resolution (_up) form, so FPN / PSPNet keep
+            # their stp_resize_bilinear and its gradient launch
+            self.loss_scalars = self._alloc((16,), torch.float32)
+            self.loss_scalars.zero_()
+            dl = self._gradbuf(logits) if self.training else None
+            self._loss_weights = (C.c_float * 5)(w_cce, w_dice, w_iou, w_jaccard, w_focal)     # host array read at launch
+            self._emit(self.fwd, "stp_softmax_loss_ex", logits.buf.data_ptr(), target.buf.data_ptr(), logits.rows, logits.C, logits.C,
+                       self.cdt, C.addressof(self._loss_weights), self.loss_scalars.data_ptr(), dl.data_ptr() if dl is not None else None,
+                       logits.gradC, float(self.loss_scale), self.ws_loss.data_ptr(), self.ws_loss.numel() * 4)
+            if self.training and self.dls is not None:
+                self._emit(self.fwd, "stp_scale_by_device", dl.data_ptr(), logits.rows * logits.gradC, self.cdt, self.dls.data_ptr(), self.dls.data_ptr() + 16)
+            logits.grad_ready = self.training
             return
         self.loss_scalars = self._alloc((12,), torch.float32)
         rec = logits.meta.get("resize_rec")
@@ -1530,7 +1545,7 @@ class Plan(object):
 
     # loss launches whose third argument is the element / pixel count of the batch ([N, ...] -> the first n_valid samples)
     LOSS_LAUNCHES = ("stp_sigmoid_bce_dice", "stp_softmax_cce_dice", "stp_prob_bce_dice", "stp_sigmoid_loss_ex", "stp_prob_cce_dice",
-                     "stp_sigmoid_multilabel_loss")
+                     "stp_sigmoid_multilabel_loss", "stp_softmax_loss_ex")
 
     def rerun_loss(self, n_valid):
         """Re-evaluates the loss / metric reduction over the first ``n_valid`` samples only (an evaluation batch whose tail

@@ -666,20 +666,25 @@ def _feed_block(self, plan, hb):
 DeviceFeeder._feed_block = _feed_block
 
 
-def derived_metrics(scal, classes=1, extended=False, activation=None):
+def derived_metrics(scal, classes=1, extended=False, activation=None, unlogged=()):
     """scal: the loss scalars of stp_sigmoid_bce_dice -> Keras-style log entries (metric names of
     schemas/segmentation.raml:98-105: binary_accuracy, dice, iou, iot).  ``extended``: the loss names one of the other registry
-    entries (stp_sigmoid_loss_ex / stp_lovasz_hinge leave them in scalars 10..12): they are logged too, so that
+    entries (stp_sigmoid_loss_ex / stp_lovasz_hinge / stp_sigmoid_multilabel_loss / stp_softmax_loss_ex leave them in scalars 10..12): they are logged too, so that
     ``primary_metric: val_focal_loss`` or a callback monitoring it sees the quantity it names.  The names follow the head's
-    activation: a multi-label sigmoid head (``activation="sigmoid"``, classes > 1) logs binary_crossentropy and has no lovasz_loss."""
+    activation: a multi-label sigmoid head (``activation="sigmoid"``, classes > 1) logs binary_crossentropy, a softmax head
+    categorical_crossentropy; only the one-class head has lovasz_loss.  ``unlogged``: names left out because the loss kernel did not
+    evaluate them (``HipSegModel.unevaluated_terms``: focal_loss of a softmax head whose spec gives it no weight - stp_softmax_loss_ex
+    skips the term, and a constant 0 must not be logged, monitored or selected on)."""
     loss, bce, dice_l, dice_m, acc, _sp, _sy, _spy, iou, iot = (float(v) for v in scal[:10])
     multilabel = is_multilabel(classes, activation)
     out = {"loss": loss, ("binary_crossentropy" if classes == 1 or multilabel else "categorical_crossentropy"): bce, "dice_loss": dice_l,
            "dice": dice_m, "binary_accuracy": acc, "iou": iou, "iot": iot}
     if extended and len(scal) >= 13:
         out.update(iou_loss=1.0 - iou, jaccard_loss=float(scal[10]), focal_loss=float(scal[11]))
-        if not multilabel:
+        if classes == 1:
             out["lovasz_loss"] = float(scal[12])
+        for k in unlogged:
+            out.pop(k, None)
     return out
 
 
@@ -689,6 +694,10 @@ def _extended(model):
 
 def _activation(model):
     return getattr(model, "head_activation", None)
+
+
+def _unlogged(model):
+    return tuple(getattr(model, "unevaluated_terms", ()))
 
 
 class Trainer(object):
@@ -764,7 +773,7 @@ class Trainer(object):
         sums = {}
         if snaps:
             for scal, n in zip(torch.stack(snaps).cpu().numpy(), counts):
-                for k, v in derived_metrics(scal, getattr(m, "classes", 1), _extended(m), _activation(m)).items():
+                for k, v in derived_metrics(scal, getattr(m, "classes", 1), _extended(m), _activation(m), _unlogged(m)).items():
                     sums[k] = sums.get(k, 0.0) + v * n
         return sums, int(sum(counts))
 
@@ -772,17 +781,17 @@ class Trainer(object):
         """Sample-weighted epoch means, combined over all ranks (one small SUM-all-reduce per call): every rank returns
         the same values bit for bit."""
         sums, n = self.run_epoch_sums(indexes, training)
-        return reduce_epoch_sums(sums, n, getattr(self.model, "classes", 1), _extended(self.model), _activation(self.model))
+        return reduce_epoch_sums(sums, n, getattr(self.model, "classes", 1), _extended(self.model), _activation(self.model), _unlogged(self.model))
 
 
-def epoch_log_names(classes=1, extended=False, activation=None):
-    return sorted(derived_metrics(np.zeros(16, np.float32), classes, extended, activation))
+def epoch_log_names(classes=1, extended=False, activation=None, unlogged=()):
+    return sorted(derived_metrics(np.zeros(16, np.float32), classes, extended, activation, unlogged))
 
 
-def reduce_epoch_sums(sums, n, classes=1, extended=False, activation=None):
+def reduce_epoch_sums(sums, n, classes=1, extended=False, activation=None, unlogged=()):
     """{name: weighted sum}, samples -> {name: mean over the samples of ALL ranks}.  The vector layout is fixed by the
     metric names (not by what a rank happened to see), so a rank with an empty shard still takes part in the collective."""
-    names = epoch_log_names(classes, extended, activation)
+    names = epoch_log_names(classes, extended, activation, unlogged)
     vec = distributed.allreduce_sums([sums.get(k, 0.0) for k in names] + [float(n)])
     total = vec[-1]
     if total <= 0:
@@ -1031,7 +1040,7 @@ class GenericTaskConfig(object):
         # primary_metric / callback monitors are checked against the names an epoch will log BEFORE the first epoch trains (a typo used
         # to surface only after a whole epoch: advisor finding, round 3)
         known = {}
-        for k in epoch_log_names(self.classes, _extended(impl), _activation(impl)) + ["lr"]:
+        for k in epoch_log_names(self.classes, _extended(impl), _activation(impl), _unlogged(impl)) + ["lr"]:
             known[k] = 0.0
             known["val_" + k] = 0.0
         for what, name in [("primary_metric", self.primary_metric)] + [("%s.monitor" % type(cb).__name__, cb.monitor) for cb in cbs if hasattr(cb, "monitor")]:
