@@ -302,7 +302,7 @@ int stp_wgrad_group_reduce(const void* host_table, const void* dev_table, const 
  *   bwd : [Cin_pad16][KH][KW][CoutB]  dtype, spatially flipped and transposed, zero padded
  *         (operand of the data-gradient GEMM: stp_conv2d over dY with pad' = K-1-pad)
  * Either pointer may be NULL.  stp_weight_grad_unpad copies a padded gradient
- * [Cout..][KH][KWp][Cinp] back to the master layout.  stp_stem_beta_grad: see loss_optim.hip.
+ * [Cout..][KH][KWp][Cinp] back to the master layout.  stp_stem_beta_grad: see weight_prep.hip.
  */
 int stp_weight_prepare(const float* master, void* fwd, void* bwd, int32_t Cout, int32_t KH, int32_t KW,
                        int32_t Cin, int32_t KWp, int32_t Cinp, int32_t CoutB, int32_t dtype, void* stream);

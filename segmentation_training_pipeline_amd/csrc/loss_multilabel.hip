@@ -8,10 +8,9 @@
 // pixel, the class loop unrolled to CM = 4 or 8 and predicated, rows read in 16- / 8-byte chunks where the stride allows): value pass
 // -> per-workgroup partials -> finalize (12 scalars) -> gradient pass, which leaves one partial sum PER CLASS per workgroup for
 // stp_sigmoid_multilabel_bias_grad.  Plain global (not buffer) loads and stores: no register-soffset store hazard (tests/test_isa_multilabel.py).
-#include "common.h"
+#include "loss_reduce.h"
 
 #define ML_MAX_CLASSES 8
-#define ML_MAX_BLOCKS 1024           // value-pass workgroups: 16 partial floats each (stp_loss_workspace_bytes covers 1024 x 16)
 #define ML_NSUM 16
 // gradient-pass workgroups: their 8 per-class sums reuse the value pass's partial area (1024 x 16 floats = 2048 x 8), which the
 // finalize launch has consumed before the gradient pass starts (same stream)
@@ -22,17 +21,6 @@
 // ZMAX = log((1 - eps) / eps), and exp(-|zc|) = max(exp(-|z|), EMIN) with EMIN = eps / (1 - eps)
 #define ML_ZMAX 16.11809555f
 #define ML_EMIN 1.0000001e-7f
-
-struct MlWeights { float w[5]; };
-
-static int ml_value_blocks(int64_t pixels) {
-  int64_t b = pixels / 1024;
-  return (int)(b < 1 ? 1 : b > ML_MAX_BLOCKS ? ML_MAX_BLOCKS : b);
-}
-static int ml_grad_blocks(int64_t pixels) {
-  const int64_t g = (pixels + 255) / 256;
-  return (int)(g > ML_GRAD_MAX_BLOCKS ? ML_GRAD_MAX_BLOCKS : g);
-}
 
 // one row of logits -> p[0 .. CM), zeros beyond `classes`.  CB = bytes per load (16, 8, or 0 = element by element); the host picks a
 // CB that divides the row stride and the base alignment, and CB / sizeof(T) <= CM, so every chunk that holds a used channel lies in the row.
@@ -133,74 +121,27 @@ __global__ __launch_bounds__(256) void ml_partial_kernel(const T* __restrict__ l
     ml_row_load<T, CM, CB>(logits + i * ldc, classes, p0);
     pixel(p0, target[i]);
   }
-  __shared__ float red[4][9];
-#pragma unroll
-  for (int e = 0; e < 9; ++e) a[e] = wave_sum(a[e]);
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int e = 0; e < 9; ++e) red[threadIdx.x >> 6][e] = a[e];
-  __syncthreads();
-  if (threadIdx.x < ML_NSUM)
-    partial[(size_t)blockIdx.x * ML_NSUM + threadIdx.x] =
-        threadIdx.x < 9 ? (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]) : 0.f;
+  loss_block_sums<ML_NSUM, 9, LOSS_WAVES_PAIRWISE>(a, partial);
 }
 
 // the 12 scalars of stp_sigmoid_loss_ex: 0 loss 1 bce 2 dice_loss 3 dice 4 binary_accuracy 5 sum_p 6 sum_y 7 sum_py 8 iou 9 iot
 // 10 jaccard_loss 11 focal_loss - element means over pixels * classes, jaccard over pixels
-__global__ __launch_bounds__(256) void ml_finalize_kernel(const float* partial, int blocks, double inv_elems, double inv_pixels, MlWeights lw,
+__global__ __launch_bounds__(256) void ml_finalize_kernel(const float* partial, int blocks, double inv_elems, double inv_pixels, LossWeights lw,
                                                           float* scalars) {
-  __shared__ double sh[16][ML_NSUM];
-  const int e = threadIdx.x & 15, lane = threadIdx.x >> 4;
-  double a = 0.0;
-  {
-    int b = lane;
-    for (; b + 48 < blocks; b += 64) {        // four partials in flight (a run-time trip count keeps one); fixed order of additions
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = partial[(size_t)(b + 16 * u) * ML_NSUM + e];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) a += (double)v[u];
-    }
-    for (; b < blocks; b += 16) a += (double)partial[(size_t)b * ML_NSUM + e];
-  }
-  sh[lane][e] = a;
-  __syncthreads();
-  for (int w = 8; w > 0; w >>= 1) {
-    if (lane < w) sh[lane][e] += sh[lane + w][e];
-    __syncthreads();
-  }
+  const double* s = loss_finalize_sums<ML_NSUM>(partial, blocks);
   if (threadIdx.x != 0) return;
-  const double* s = sh[0];
-  const double bce = s[0] * inv_elems;
-  const double dice_l = 1.0 - (2.0 * s[3] + 1.0) / (s[2] + s[1] + 1.0);
-  const double iou = (s[3] + 1.0) / (s[2] + s[1] - s[3] + 1.0);
-  const double jac = s[7] * inv_pixels, focal = s[8] * inv_elems;
-  scalars[0] = (float)(lw.w[0] * bce + lw.w[1] * dice_l + lw.w[2] * (1.0 - iou) + lw.w[3] * jac + lw.w[4] * focal);
-  scalars[1] = (float)bce;
-  scalars[2] = (float)dice_l;
-  scalars[3] = (float)((2.0 * s[5] + 1.0) / (s[2] + s[4] + 1.0));
-  scalars[4] = (float)(s[6] * inv_elems);
-  scalars[5] = (float)s[1];
-  scalars[6] = (float)s[2];
-  scalars[7] = (float)s[3];
-  scalars[8] = (float)iou;
-  scalars[9] = (float)((s[5] + 1.0) / (s[2] + s[4] - s[5] + 1.0));
-  scalars[10] = (float)jac;
-  scalars[11] = (float)focal;
+  loss_ex_scalars(s, loss_common_scalars(s, inv_elems, inv_elems, scalars), lw, inv_pixels, inv_elems, scalars);
 }
 
 // gradient pass: dL/dlogit of the `classes` channels x grad_scale into [pixels][dlc] (padding channels 0); one partial sum per class of the
 // STORED values per workgroup -> gsum[block][8].  VEC_OUT: dlc is a multiple of 16 bytes (the plan's padded gradient rows) - 16-byte stores.
 template <typename T, int CM, int CB, bool VEC_OUT>
 __global__ __launch_bounds__(256) void ml_grad_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ target, int64_t pixels,
-                                                      int classes, int ldc, const float* __restrict__ scalars, MlWeights lw, float inv_elems,
+                                                      int classes, int ldc, const float* __restrict__ scalars, LossWeights lw, float inv_elems,
                                                       float inv_pixels, float grad_scale, T* __restrict__ dl, int dlc, float* __restrict__ gsum) {
   constexpr int V = Elem<T>::VEC;
-  const float sp = scalars[5], sy = scalars[6], spy = scalars[7];
-  const float den = sy + sp + 1.f, num = 2.f * spy + 1.f;
-  const float inv_den2 = 1.f / (den * den);
-  const float uden = sy + sp - spy + 1.f, unum = spy + 1.f;          // iou_coef = unum / uden
-  const float inv_uden2 = 1.f / (uden * uden);
+  const DiceIouGrad k(scalars);
+  const float den = k.den, inv_den2 = k.inv_den2, num = k.num, uden = k.uden, unum = k.unum, inv_uden2 = k.inv_uden2;
   const bool focal = lw.w[4] != 0.f;
   float acc[CM];
 #pragma unroll
@@ -283,50 +224,25 @@ __global__ __launch_bounds__(256) void ml_grad_kernel(const T* __restrict__ logi
       for (int c = classes; c < dlc; ++c) Elem<T>::store(o + c, 0.f);
     }
   }
-  __shared__ float wred[4][ML_MAX_CLASSES];
-#pragma unroll
-  for (int c = 0; c < CM; ++c) acc[c] = wave_sum(acc[c]);
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int c = 0; c < CM; ++c) wred[threadIdx.x >> 6][c] = acc[c];
-  __syncthreads();
-  if (threadIdx.x < ML_MAX_CLASSES)
-    gsum[(size_t)blockIdx.x * ML_MAX_CLASSES + threadIdx.x] =
-        threadIdx.x < CM ? (wred[0][threadIdx.x] + wred[1][threadIdx.x]) + (wred[2][threadIdx.x] + wred[3][threadIdx.x]) : 0.f;
+  loss_block_sums<ML_MAX_CLASSES, CM, LOSS_WAVES_PAIRWISE, ML_MAX_CLASSES>(acc, gsum);
 }
 
 // dbias[c] (+)= sum over the gradient workgroups of gsum[block][c]: 8 classes x 32 strided lanes, then a fixed-shape LDS tree
 __global__ __launch_bounds__(256) void ml_bias_grad_kernel(const float* gsum, int blocks, int classes, float* dbias, int accumulate) {
-  __shared__ double sh[32][ML_MAX_CLASSES];
-  const int c = threadIdx.x & 7, lane = threadIdx.x >> 3;
-  double a = 0.0;
-  int b = lane;
-  for (; b + 224 < blocks; b += 256) {        // eight partials in flight; fixed order of additions
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = gsum[(size_t)(b + 32 * u) * ML_MAX_CLASSES + c];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) a += (double)v[u];
-  }
-  for (; b < blocks; b += 32) a += (double)gsum[(size_t)b * ML_MAX_CLASSES + c];
-  sh[lane][c] = a;
-  __syncthreads();
-  for (int w = 16; w > 0; w >>= 1) {
-    if (lane < w) sh[lane][c] += sh[lane + w][c];
-    __syncthreads();
-  }
-  if (threadIdx.x < (unsigned)classes) dbias[c] = accumulate ? dbias[c] + (float)sh[0][c] : (float)sh[0][c];
+  const double* s = loss_finalize_sums<ML_MAX_CLASSES>(gsum, blocks);
+  const int c = threadIdx.x & 7;
+  if (threadIdx.x < (unsigned)classes) dbias[c] = accumulate ? dbias[c] + (float)s[c] : (float)s[c];
 }
 
 template <typename T, int CM, int CB>
-static void ml_launch(const T* logits, const uint8_t* target, int64_t pixels, int classes, int ldc, const MlWeights& lw, float* scalars,
+static void ml_launch(const T* logits, const uint8_t* target, int64_t pixels, int classes, int ldc, const LossWeights& lw, float* scalars,
                       T* dl, int dlc, bool vec_out, float grad_scale, float* ws, hipStream_t s) {
-  const int blocks = ml_value_blocks(pixels);
+  const int blocks = loss_value_blocks(pixels);
   hipLaunchKernelGGL((ml_partial_kernel<T, CM, CB>), dim3(blocks), dim3(256), 0, s, logits, target, pixels, classes, ldc, ws);
   hipLaunchKernelGGL(ml_finalize_kernel, dim3(1), dim3(256), 0, s, ws, blocks, 1.0 / ((double)pixels * classes), 1.0 / (double)pixels, lw,
                      scalars);
   if (!dl) return;
-  const int g = ml_grad_blocks(pixels);
+  const int g = loss_grad_blocks(pixels, ML_GRAD_MAX_BLOCKS);
   const float inv_elems = (float)(1.0 / ((double)pixels * classes)), inv_pixels = (float)(1.0 / (double)pixels);
   if (vec_out)
     hipLaunchKernelGGL((ml_grad_kernel<T, CM, CB, true>), dim3(g), dim3(256), 0, s, logits, target, pixels, classes, ldc, scalars, lw,
@@ -338,7 +254,7 @@ static void ml_launch(const T* logits, const uint8_t* target, int64_t pixels, in
 
 // picks the class bucket and the widest row load the stride and the base alignment allow
 template <typename T>
-static void ml_dispatch(const T* logits, const uint8_t* target, int64_t pixels, int classes, int ldc, const MlWeights& lw, float* scalars,
+static void ml_dispatch(const T* logits, const uint8_t* target, int64_t pixels, int classes, int ldc, const LossWeights& lw, float* scalars,
                         T* dl, int dlc, float grad_scale, float* ws, hipStream_t s) {
   const size_t row = (size_t)ldc * sizeof(T);
   const uintptr_t base = reinterpret_cast<uintptr_t>(logits);
@@ -359,19 +275,16 @@ static void ml_dispatch(const T* logits, const uint8_t* target, int64_t pixels, 
 extern "C" int stp_sigmoid_multilabel_loss(const void* logits, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc,
                                            int32_t dtype, const float* weights5, float* scalars, void* dlogits, int32_t dl_channels,
                                            float grad_scale, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!stp_dtype_ok(dtype)) return STP_E_BADARG;      // (the other build's 16-bit code, or garbage)
-  if (!logits || !target || !weights5 || !scalars || !workspace || pixels <= 0) return STP_E_BADARG;
-  if (classes < 2 || classes > ML_MAX_CLASSES || ldc < classes || dl_channels < classes) return STP_E_BADARG;
-  if (workspace_bytes < stp_loss_workspace_bytes()) return STP_E_WORKSPACE;
-  MlWeights lw;
-  for (int i = 0; i < 5; ++i) lw.w[i] = weights5[i];
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == STP_H16)
-    ml_dispatch<bf16_t>((const bf16_t*)logits, target, pixels, classes, ldc, lw, scalars, (bf16_t*)dlogits, dl_channels, grad_scale,
-                        (float*)workspace, s);
-  else
-    ml_dispatch<float>((const float*)logits, target, pixels, classes, ldc, lw, scalars, (float*)dlogits, dl_channels, grad_scale,
-                       (float*)workspace, s);
+  const int rc = loss_check(dtype, logits && target && weights5 && scalars && workspace && pixels > 0 && classes >= 2 && classes <= ML_MAX_CLASSES &&
+                                       ldc >= classes && dl_channels >= classes,
+                            workspace_bytes, stp_loss_workspace_bytes());
+  if (rc != STP_OK) return rc;
+  const LossWeights lw = loss_weights(weights5);
+  loss_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    ml_dispatch<T>((const T*)logits, target, pixels, classes, ldc, lw, scalars, (T*)dlogits, dl_channels, grad_scale, (float*)workspace,
+                   (hipStream_t)stream);
+  });
   STP_LAUNCH_CHECK();
   return STP_OK;
 }
@@ -379,7 +292,7 @@ extern "C" int stp_sigmoid_multilabel_loss(const void* logits, const uint8_t* ta
 extern "C" int stp_sigmoid_multilabel_bias_grad(const void* workspace, int64_t pixels, int32_t classes, float* dbias, int32_t accumulate,
                                                 void* stream) {
   if (!workspace || !dbias || pixels <= 0 || classes < 2 || classes > ML_MAX_CLASSES) return STP_E_BADARG;
-  hipLaunchKernelGGL(ml_bias_grad_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, ml_grad_blocks(pixels), classes,
+  hipLaunchKernelGGL(ml_bias_grad_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, loss_grad_blocks(pixels, ML_GRAD_MAX_BLOCKS), classes,
                      dbias, accumulate);
   STP_LAUNCH_CHECK();
   return STP_OK;

@@ -1,6 +1,6 @@
 // Multi-class softmax head with the whole loss registry but lovasz_loss: the weighted sum of categorical_crossentropy, dice_loss,
 // iou_loss, jaccard_loss and focal_loss (oracle/losses.py) on p = softmax(z) and the one-hot y of the target class t, classes = 2..32:
-//   categorical_crossentropy / dice_loss   exactly the forms of softmax_loss_partial_kernel / softmax_loss_grad_kernel (loss_optim.hip)
+//   categorical_crossentropy / dice_loss   exactly the forms of softmax_loss_partial_kernel / softmax_loss_grad_kernel (loss_softmax.hip)
 //   iou_loss      1 - (I + 1) / U with I = sum p_t and U = pixels + sum p - I + 1: the sums the value pass takes anyway
 //   jaccard_loss  per pixel 100 (1 - a / b), a = p_t + 100, b = 101 + sum_c p_c - p_t, mean over pixels - no class loop
 //   focal_loss    gamma 2, alpha 0.25, q = clip(p, 1e-7, 1 - 1e-7): -0.25 (1 - q)^2 log q for c == t, -0.75 q^2 log(1 - q) otherwise, both
@@ -11,15 +11,13 @@
 // order, no atomics) -> one-workgroup finalize in double (12 scalars, the layout of stp_sigmoid_loss_ex) -> gradient pass.  The passes
 // are VALU-bound (see softmax_row.h), so the weights - launch-uniform - pick an INSTANCE: the focal class loops and the iou / jaccard
 // terms are compiled out when their weights are zero.
+#include "loss_reduce.h"
 #include "softmax_row.h"
 
 #define SMX_NSUM 16
-#define SMX_MAX_BLOCKS 1024          // value-pass workgroups (stp_loss_workspace_bytes covers 1024 x 16 floats)
 #define SMX_GRAD_MAX_BLOCKS 4096
 #define SMX_JACCARD_SMOOTH 100.f
 #define SMX_FOCAL_ALPHA 0.25f
-
-struct SmxWeights { float w[5]; };   // categorical_crossentropy, dice_loss, iou_loss, jaccard_loss, focal_loss
 
 // 1 - p_c without cancellation: at most one probability of a row exceeds 0.5 - for the largest one (index *imax) 1 - p is the sum of
 // the OTHERS (returned), for every other class 1 - p_c >= 0.5 is exact enough as written.  A confidently wrong pixel (a class that is not
@@ -52,22 +50,10 @@ __global__ __launch_bounds__(256) void smx_partial_kernel(const T* __restrict__ 
     float p[CM];
     softmax_row<T, CM>(logits + i * ldc, classes, vec, p, vec4);
     const int t = target[i] < classes ? target[i] : classes - 1;
-    // the per-class sums of the one-hot target in closed form, as softmax_loss_partial_kernel takes them
-    float pt = 0.f, pmax = 0.f, psum = 0.f;
-#pragma unroll
-    for (int c = 0; c < CM; ++c) {
-      pt = c == t ? p[c] : pt;
-      pmax = fmaxf(pmax, p[c]);                      // (p[c] = 0 beyond `classes`)
-      psum += p[c];
-    }
-    const float tt = pt > 0.5f ? 1.f : 0.f, tm = pmax > 0.5f ? 1.f : 0.f;
+    float pt, pmax, psum;
+    softmax_row_stats(p, t, pt, pmax, psum);
     a[1] += psum;
-    a[2] += 1.f;
-    a[3] += pt;
-    a[4] += tm;
-    a[5] += tt;
-    a[6] += (float)classes - (pt > 0.5f ? 0.f : 1.f + tm);
-    a[0] += -__logf(fminf(fmaxf(pt, 1e-7f), 1.f - 1e-7f));
+    softmax_pixel_sums(a, pt, pmax, classes);
     // jaccard: 1 - a / b = (b - a) / b with b - a = 1 + sum_c p_c - 2 p_t (no cancellation against the smooth term)
     a[7] += SMX_JACCARD_SMOOTH * __fdividef(1.f + psum - 2.f * pt, SMX_JACCARD_SMOOTH + 1.f + psum - pt);
     if constexpr (FOCAL) {
@@ -85,60 +71,16 @@ __global__ __launch_bounds__(256) void smx_partial_kernel(const T* __restrict__ 
       a[8] += f;
     }
   }
-  __shared__ float red[4][9];
-#pragma unroll
-  for (int e = 0; e < 9; ++e) a[e] = wave_sum(a[e]);
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int e = 0; e < 9; ++e) red[threadIdx.x >> 6][e] = a[e];
-  __syncthreads();
-  if (threadIdx.x < SMX_NSUM)
-    partial[(size_t)blockIdx.x * SMX_NSUM + threadIdx.x] =
-        threadIdx.x < 9 ? red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x] : 0.f;
+  loss_block_sums<SMX_NSUM>(a, partial);
 }
 
 // the 12 scalars of stp_sigmoid_loss_ex: 0 loss 1 categorical_crossentropy 2 dice_loss 3 dice 4 accuracy 5 sum_p 6 sum_y 7 sum_py 8 iou
 // 9 iot 10 jaccard_loss 11 focal_loss; 1..9 as softmax_loss_finalize_kernel defines them
-__global__ __launch_bounds__(256) void smx_finalize_kernel(const float* partial, int blocks, double inv_pixels, double inv_elems, SmxWeights lw,
+__global__ __launch_bounds__(256) void smx_finalize_kernel(const float* partial, int blocks, double inv_pixels, double inv_elems, LossWeights lw,
                                                            float* scalars) {
-  __shared__ double sh[16][SMX_NSUM];
-  const int e = threadIdx.x & 15, lane = threadIdx.x >> 4;
-  double a = 0.0;
-  {
-    int b = lane;
-    for (; b + 48 < blocks; b += 64) {        // four partials in flight (a run-time trip count keeps one); fixed order of additions
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = partial[(size_t)(b + 16 * u) * SMX_NSUM + e];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) a += (double)v[u];
-    }
-    for (; b < blocks; b += 16) a += (double)partial[(size_t)b * SMX_NSUM + e];
-  }
-  sh[lane][e] = a;
-  __syncthreads();
-  for (int w = 8; w > 0; w >>= 1) {
-    if (lane < w) sh[lane][e] += sh[lane + w][e];
-    __syncthreads();
-  }
+  const double* s = loss_finalize_sums<SMX_NSUM>(partial, blocks);
   if (threadIdx.x != 0) return;
-  const double* s = sh[0];
-  const double cce = s[0] * inv_pixels;
-  const double dice_l = 1.0 - (2.0 * s[3] + 1.0) / (s[2] + s[1] + 1.0);
-  const double iou = (s[3] + 1.0) / (s[2] + s[1] - s[3] + 1.0);
-  const double jac = s[7] * inv_pixels, focal = s[8] * inv_elems;
-  scalars[0] = (float)(lw.w[0] * cce + lw.w[1] * dice_l + lw.w[2] * (1.0 - iou) + lw.w[3] * jac + lw.w[4] * focal);
-  scalars[1] = (float)cce;
-  scalars[2] = (float)dice_l;
-  scalars[3] = (float)((2.0 * s[5] + 1.0) / (s[2] + s[4] + 1.0));
-  scalars[4] = (float)(s[6] * inv_elems);
-  scalars[5] = (float)s[1];
-  scalars[6] = (float)s[2];
-  scalars[7] = (float)s[3];
-  scalars[8] = (float)iou;
-  scalars[9] = (float)((s[5] + 1.0) / (s[2] + s[4] - s[5] + 1.0));
-  scalars[10] = (float)jac;
-  scalars[11] = (float)focal;
+  loss_ex_scalars(s, loss_common_scalars(s, inv_pixels, inv_elems, scalars), lw, inv_pixels, inv_elems, scalars);
 }
 
 // gradient pass: dL/dlogit of the `classes` channels x grad_scale into [pixels][dlc], padding channels exactly 0.
@@ -146,16 +88,11 @@ __global__ __launch_bounds__(256) void smx_finalize_kernel(const float* partial,
 template <typename T, int CM, bool EXT, bool FOCAL>
 __global__ __launch_bounds__(256) void smx_grad_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ target, int64_t pixels,
                                                        int classes, int ldc, bool vec, bool vec4, const float* __restrict__ scalars,
-                                                       SmxWeights lw, float inv_pixels, float inv_elems, float grad_scale,
+                                                       LossWeights lw, float inv_pixels, float inv_elems, float grad_scale,
                                                        T* __restrict__ dl, int dlc, bool vout) {
-  constexpr int V = Elem<T>::VEC;
   const float w_cce = lw.w[0], w_dice = lw.w[1];
-  const float sp = scalars[5], sy = scalars[6], spy = scalars[7];
-  const float den = sy + sp + 1.f;
-  const float inv_den2 = 1.f / (den * den);
-  const float num = 2.f * spy + 1.f;
-  const float uden = sy + sp - spy + 1.f, unum = spy + 1.f;          // iou_coef = unum / uden
-  const float inv_uden2 = 1.f / (uden * uden);
+  const DiceIouGrad k(scalars);
+  const float den = k.den, inv_den2 = k.inv_den2, num = k.num, uden = k.uden, unum = k.unum, inv_uden2 = k.inv_uden2;
   // iou: d / dp_c = -(y_c U - (I + 1)(1 - y_c)) / U^2 -> one value for the target class, one for the others
   const float iou1 = -lw.w[2] * uden * inv_uden2, iou0 = lw.w[2] * unum * inv_uden2;
   const float wf = lw.w[4] * inv_elems;
@@ -218,42 +155,12 @@ __global__ __launch_bounds__(256) void smx_grad_kernel(const T* __restrict__ log
       if constexpr (FOCAL) v += c == imax ? umax - p[c] * hrest : g[c] - p[c] * hrest - umax * (p[c] * rr);
       g[c] = c < classes ? v * grad_scale : 0.f;
     }
-    T* o = dl + i * dlc;
-    if (vout) {
-#pragma unroll
-      for (int v = 0; v < 32 / V; ++v) {
-        if (v * V >= dlc) break;
-        u32x4 r = {0u, 0u, 0u, 0u};
-        auto gv = [&](int idx) { return idx < CM ? g[idx % CM] : 0.f; };      // channels past the class bucket are padding
-        if constexpr (sizeof(T) == 2) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) r[e] = pack_bf16x2(gv(v * V + 2 * e), gv(v * V + 2 * e + 1));
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) r[e] = __float_as_uint(gv(v * V + e));
-        }
-        *reinterpret_cast<u32x4*>(o + v * V) = r;
-      }
-      for (int c = 32; c < dlc; c += V) *reinterpret_cast<u32x4*>(o + c) = u32x4{0u, 0u, 0u, 0u};
-    } else {
-#pragma unroll
-      for (int c = 0; c < CM; ++c) if (c < classes) Elem<T>::store(o + c, g[c]);
-      for (int c = classes; c < dlc; ++c) Elem<T>::store(o + c, 0.f);
-    }
+    softmax_grad_row_store<T, CM, true>(dl + i * dlc, g, classes, dlc, vout);
   }
 }
 
-static int smx_value_blocks(int64_t pixels) {
-  const int64_t b = pixels / 1024;
-  return (int)(b < 1 ? 1 : b > SMX_MAX_BLOCKS ? SMX_MAX_BLOCKS : b);
-}
-static int smx_grad_blocks(int64_t pixels) {
-  const int64_t g = (pixels + 255) / 256;
-  return (int)(g > SMX_GRAD_MAX_BLOCKS ? SMX_GRAD_MAX_BLOCKS : g);
-}
-
 template <typename T, int CM>
-static void smx_launch(const T* logits, const uint8_t* target, int64_t pixels, int classes, int ldc, const SmxWeights& lw, float* scalars,
+static void smx_launch(const T* logits, const uint8_t* target, int64_t pixels, int classes, int ldc, const LossWeights& lw, float* scalars,
                        T* dl, int dlc, float grad_scale, float* ws, hipStream_t s) {
   constexpr int V = Elem<T>::VEC;
   // the widest row access the stride and the base alignment allow: 16 bytes, 8 bytes (16-bit rows of 4 k elements), element by element
@@ -261,7 +168,7 @@ static void smx_launch(const T* logits, const uint8_t* target, int64_t pixels, i
   const bool vec = (ldc % V) == 0 && CM % V == 0 && (base & 15) == 0;
   const bool vec4 = !vec && sizeof(T) == 2 && (ldc % 4) == 0 && (CM % 4) == 0 && (base & 7) == 0;
   const bool focal = lw.w[4] != 0.f, ext = lw.w[2] != 0.f || lw.w[3] != 0.f;
-  const int blocks = smx_value_blocks(pixels);
+  const int blocks = loss_value_blocks(pixels);
   const double inv_pixels = 1.0 / (double)pixels, inv_elems = 1.0 / ((double)pixels * classes);
   if (focal)
     hipLaunchKernelGGL((smx_partial_kernel<T, CM, true>), dim3(blocks), dim3(256), 0, s, logits, target, pixels, classes, ldc, vec, vec4, ws);
@@ -270,7 +177,7 @@ static void smx_launch(const T* logits, const uint8_t* target, int64_t pixels, i
   hipLaunchKernelGGL(smx_finalize_kernel, dim3(1), dim3(256), 0, s, ws, blocks, inv_pixels, inv_elems, lw, scalars);
   if (!dl) return;
   const bool vout = (dlc % V) == 0 && (reinterpret_cast<uintptr_t>(dl) & 15) == 0;
-  const int g = smx_grad_blocks(pixels);
+  const int g = loss_grad_blocks(pixels, SMX_GRAD_MAX_BLOCKS);
 #define SMX_GRAD(EXT, FOCAL)                                                                                                              \
   hipLaunchKernelGGL((smx_grad_kernel<T, CM, EXT, FOCAL>), dim3(g), dim3(256), 0, s, logits, target, pixels, classes, ldc, vec, vec4, scalars, \
                      lw, (float)inv_pixels, (float)inv_elems, grad_scale, dl, dlc, vout)
@@ -282,34 +189,21 @@ static void smx_launch(const T* logits, const uint8_t* target, int64_t pixels, i
 #undef SMX_GRAD
 }
 
-template <typename T>
-static void smx_dispatch(const T* logits, const uint8_t* target, int64_t pixels, int classes, int ldc, const SmxWeights& lw, float* scalars,
-                         T* dl, int dlc, float grad_scale, float* ws, hipStream_t s) {
-#define SMX_GO(CM) smx_launch<T, CM>(logits, target, pixels, classes, ldc, lw, scalars, dl, dlc, grad_scale, ws, s)
-  if (classes <= 4) SMX_GO(4);
-  else if (classes <= 8) SMX_GO(8);
-  else if (classes <= 16) SMX_GO(16);
-  else if (classes <= 24) SMX_GO(24);
-  else SMX_GO(32);
-#undef SMX_GO
-}
-
 extern "C" int stp_softmax_loss_ex(const void* logits, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype,
                                    const float* weights5, float* scalars, void* dlogits, int32_t dl_channels, float grad_scale,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-  if (!stp_dtype_ok(dtype)) return STP_E_BADARG;      // (the other build's 16-bit code, or garbage)
-  if (!logits || !target || !weights5 || !scalars || !workspace || pixels <= 0) return STP_E_BADARG;
-  if (classes < 2 || classes > STP_MAX_CLASSES || ldc < classes || dl_channels < classes) return STP_E_BADARG;
-  if (workspace_bytes < stp_loss_workspace_bytes()) return STP_E_WORKSPACE;
-  SmxWeights lw;
-  for (int i = 0; i < 5; ++i) lw.w[i] = weights5[i];
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == STP_H16)
-    smx_dispatch<bf16_t>((const bf16_t*)logits, target, pixels, classes, ldc, lw, scalars, (bf16_t*)dlogits, dl_channels, grad_scale,
-                         (float*)workspace, s);
-  else
-    smx_dispatch<float>((const float*)logits, target, pixels, classes, ldc, lw, scalars, (float*)dlogits, dl_channels, grad_scale,
-                        (float*)workspace, s);
+  const int rc = loss_check(dtype, logits && target && weights5 && scalars && workspace && pixels > 0 && classes >= 2 && classes <= STP_MAX_CLASSES &&
+                                       ldc >= classes && dl_channels >= classes,
+                            workspace_bytes, stp_loss_workspace_bytes());
+  if (rc != STP_OK) return rc;
+  const LossWeights lw = loss_weights(weights5);
+  loss_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    loss_by_class_bucket(classes, [&](auto bucket) {
+      smx_launch<T, decltype(bucket)::value>((const T*)logits, target, pixels, classes, ldc, lw, scalars, (T*)dlogits, dl_channels, grad_scale,
+                                             (float*)workspace, (hipStream_t)stream);
+    });
+  });
   STP_LAUNCH_CHECK();
   return STP_OK;
 }

@@ -1,4 +1,5 @@
-// Class rows of the multi-class (softmax) head held in registers: shared by the loss kernels of loss_optim.hip and loss_softmax_ex.hip.
+// Class rows of the multi-class (softmax) head held in registers: the row load, the per-pixel sums of the value passes and the padded
+// gradient row store, shared by the loss kernels of loss_softmax.hip and loss_softmax_ex.hip.
 #pragma once
 #include "common.h"
 
@@ -59,4 +60,65 @@ template <typename T, int CM>
 __device__ __forceinline__ void softmax_row(const T* z, int classes, bool vec, float (&p)[CM], bool vec4 = false) {
   class_row_load<T, CM>(z, classes, vec, p, vec4);
   softmax_probs<CM>(p, classes);
+}
+
+// The per-class sums of the one-hot target in closed form (a loop over the classes cost ~12 instructions per class and pixel - the value
+// passes are VALU-bound: 137 us per pass for PSPNet's 20 classes against a 38 us memory floor): sum_c y_c = 1, sum_c p_c y_c = p_t, at most
+// ONE class passes the 0.5 threshold (the probabilities sum to 1), so sum_c th_c = [pmax > 0.5], sum_c th_c y_c = [p_t > 0.5] and the count
+// of th_c == y_c is classes - (p_t > 0.5 ? 0 : 1 + [pmax > 0.5]).  The counts are the same integers; sum_c p_c is added per pixel.
+// softmax_row_stats: p_t, max_c p_c and sum_c p_c of a row of probabilities.
+template <int CM>
+__device__ __forceinline__ void softmax_row_stats(const float (&p)[CM], int t, float& pt, float& pmax, float& psum) {
+  pt = 0.f; pmax = 0.f; psum = 0.f;
+#pragma unroll
+  for (int c = 0; c < CM; ++c) {
+    pt = c == t ? p[c] : pt;
+    pmax = fmaxf(pmax, p[c]);                      // (p[c] = 0 beyond `classes`)
+    psum += p[c];
+  }
+}
+// one pixel into the sums 0 cce_pixel  2 y (= 1 per pixel)  3 p_t  4 [pmax>.5]  5 [p_t>.5]  6 count of th == y.  Sum 1 (+= sum_c p_c) stays
+// with the caller: the fused form adds a product there, which contracts to one fma only while it is one expression.
+template <int N>
+__device__ __forceinline__ void softmax_pixel_sums(float (&a)[N], float pt, float pmax, int classes) {
+  const float tt = pt > 0.5f ? 1.f : 0.f, tm = pmax > 0.5f ? 1.f : 0.f;
+  a[2] += 1.f;
+  a[3] += pt;
+  a[4] += tm;
+  a[5] += tt;
+  a[6] += (float)classes - (pt > 0.5f ? 0.f : 1.f + tm);
+  // Keras: p <- p / sum(p) (a no-op on a softmax up to rounding), clip to [eps, 1-eps], -sum(y log p)
+  a[0] += -__logf(fminf(fmaxf(pt, 1e-7f), 1.f - 1e-7f));
+}
+
+// One row of the padded gradient tensor: g[0 .. classes) into o[0 .. dlc), zeros behind.  vout: dlc is a multiple of 16 bytes and the
+// rows are 16-byte aligned - whole vectors (up to the 32 channels of the widest class bucket unrolled, zero vectors beyond).  WIDE: also
+// rows wider than any class bucket (stp_softmax_loss_ex).  No plan makes such rows (gradient rows are the class count padded to 16
+// bytes, <= 32 channels), but the loop is not free: with it stp_softmax_cce_dice's gradient kernel takes 2 - 15 more vector registers
+// and loses a wave per SIMD at 24 classes, so that kernel compiles it out and leaves channels from 32 on as it always did.
+template <typename T, int CM, bool WIDE>
+__device__ __forceinline__ void softmax_grad_row_store(T* o, const float (&g)[CM], int classes, int dlc, bool vout) {
+  constexpr int V = Elem<T>::VEC;
+  if (vout) {
+#pragma unroll
+    for (int v = 0; v < 32 / V; ++v) {
+      if (v * V >= dlc) break;
+      u32x4 r = {0u, 0u, 0u, 0u};
+      auto gv = [&](int idx) { return idx < CM ? g[idx % CM] : 0.f; };      // channels past the class bucket are padding
+      if constexpr (sizeof(T) == 2) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] = pack_bf16x2(gv(v * V + 2 * e), gv(v * V + 2 * e + 1));
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] = __float_as_uint(gv(v * V + e));
+      }
+      *reinterpret_cast<u32x4*>(o + v * V) = r;
+    }
+    if constexpr (WIDE)
+      for (int c = 32; c < dlc; c += V) *reinterpret_cast<u32x4*>(o + c) = u32x4{0u, 0u, 0u, 0u};
+  } else {
+#pragma unroll
+    for (int c = 0; c < CM; ++c) if (c < classes) Elem<T>::store(o + c, g[c]);
+    for (int c = classes; c < dlc; ++c) Elem<T>::store(o + c, 0.f);
+  }
 }

@@ -1356,6 +1356,23 @@ class Plan(object):
             self._tape.append(back)
         return out
 
+    def _emit_loss(self, name, logits, target, dims, weights):
+        """The tail the loss launches on logits share: the gradient buffer (None outside training), the weights (two floats, or the
+        registry's five as a host array), `... gradC, loss_scale, workspace`, then the dynamic loss-scale multiplier.  Returns the
+        gradient buffer."""
+        dl = self._gradbuf(logits) if self.training else None
+        if len(weights) == 5:
+            self._loss_weights = (C.c_float * 5)(*weights)     # host array read at launch
+            weights = (C.addressof(self._loss_weights),)
+        else:
+            weights = tuple(float(w) for w in weights)
+        self._emit(self.fwd, name, logits.buf.data_ptr(), target.buf.data_ptr(), *dims, self.cdt, *weights, self.loss_scalars.data_ptr(),
+                   dl.data_ptr() if dl is not None else None, logits.gradC, float(self.loss_scale), self.ws_loss.data_ptr(),
+                   self.ws_loss.numel() * 4)
+        if self.training and self.dls is not None:
+            self._emit(self.fwd, "stp_scale_by_device", dl.data_ptr(), logits.rows * logits.gradC, self.cdt, self.dls.data_ptr(), self.dls.data_ptr() + 16)
+        return dl
+
     def sigmoid_loss(self, logits, target, w_bce, w_dice, w_iou=0.0, w_jaccard=0.0, w_focal=0.0, w_lovasz=0.0):
         """sigmoid + w_bce*binary_crossentropy + w_dice*dice_loss [+ w*iou_loss + w*jaccard_loss + w*focal_loss + w*lovasz_loss,
         the rest of the registry at reference segmentation.py:15-22]; seeds the backward pass."""
@@ -1366,19 +1383,10 @@ class Plan(object):
         self.loss_scalars = self._alloc((16,), torch.float32)
         self.loss_scalars.zero_()
         count = logits.rows
-        dl = self._gradbuf(logits) if self.training else None
         if w_iou or w_jaccard or w_focal:
-            import ctypes
-            self._loss_weights = (ctypes.c_float * 5)(w_bce, w_dice, w_iou, w_jaccard, w_focal)     # host array read at launch
-            self._emit(self.fwd, "stp_sigmoid_loss_ex", logits.buf.data_ptr(), target.buf.data_ptr(), count, self.cdt,
-                       ctypes.addressof(self._loss_weights), self.loss_scalars.data_ptr(), dl.data_ptr() if dl is not None else None,
-                       logits.gradC, float(self.loss_scale), self.ws_loss.data_ptr(), self.ws_loss.numel() * 4)
+            dl = self._emit_loss("stp_sigmoid_loss_ex", logits, target, (count,), (w_bce, w_dice, w_iou, w_jaccard, w_focal))
         else:
-            self._emit(self.fwd, "stp_sigmoid_bce_dice", logits.buf.data_ptr(), target.buf.data_ptr(), count, self.cdt, float(w_bce),
-                       float(w_dice), self.loss_scalars.data_ptr(), dl.data_ptr() if dl is not None else None, logits.gradC,
-                       float(self.loss_scale), self.ws_loss.data_ptr(), self.ws_loss.numel() * 4)
-        if self.training and self.dls is not None:
-            self._emit(self.fwd, "stp_scale_by_device", dl.data_ptr(), count * logits.gradC, self.cdt, self.dls.data_ptr(), self.dls.data_ptr() + 16)
+            dl = self._emit_loss("stp_sigmoid_bce_dice", logits, target, (count,), (w_bce, w_dice))
         # the class convolution reads its bias gradient from the gradient kernel's per-workgroup sums (not when another launch
         # adds to / rescales the gradient afterwards)
         logits.meta["loss_bias_grad"] = bool(self.training and not w_lovasz and self.dls is None)
@@ -1402,16 +1410,9 @@ class Plan(object):
             raise StpShapeError("multi-label loss expects 2..8 classes")
         if self.dry:
             return
-        import ctypes
         self.loss_scalars = self._alloc((16,), torch.float32)
         self.loss_scalars.zero_()
-        dl = self._gradbuf(logits) if self.training else None
-        self._loss_weights = (ctypes.c_float * 5)(w_bce, w_dice, w_iou, w_jaccard, w_focal)     # host array read at launch
-        self._emit(self.fwd, "stp_sigmoid_multilabel_loss", logits.buf.data_ptr(), target.buf.data_ptr(), logits.rows, logits.C, logits.C,
-                   self.cdt, ctypes.addressof(self._loss_weights), self.loss_scalars.data_ptr(), dl.data_ptr() if dl is not None else None,
-                   logits.gradC, float(self.loss_scale), self.ws_loss.data_ptr(), self.ws_loss.numel() * 4)
-        if self.training and self.dls is not None:
-            self._emit(self.fwd, "stp_scale_by_device", dl.data_ptr(), logits.rows * logits.gradC, self.cdt, self.dls.data_ptr(), self.dls.data_ptr() + 16)
+        self._emit_loss("stp_sigmoid_multilabel_loss", logits, target, (logits.rows, logits.C, logits.C), (w_bce, w_dice, w_iou, w_jaccard, w_focal))
         # the class convolution reads its C bias gradients from the gradient pass's per-workgroup, per-class sums (not when
         # stp_scale_by_device rescales the gradient afterwards)
         logits.meta["loss_bias_grad"] = "multilabel" if (self.training and self.dls is None) else False
@@ -1429,13 +1430,7 @@ class Plan(object):
             # their stp_resize_bilinear and its gradient launch
             self.loss_scalars = self._alloc((16,), torch.float32)
             self.loss_scalars.zero_()
-            dl = self._gradbuf(logits) if self.training else None
-            self._loss_weights = (C.c_float * 5)(w_cce, w_dice, w_iou, w_jaccard, w_focal)     # host array read at launch
-            self._emit(self.fwd, "stp_softmax_loss_ex", logits.buf.data_ptr(), target.buf.data_ptr(), logits.rows, logits.C, logits.C,
-                       self.cdt, C.addressof(self._loss_weights), self.loss_scalars.data_ptr(), dl.data_ptr() if dl is not None else None,
-                       logits.gradC, float(self.loss_scale), self.ws_loss.data_ptr(), self.ws_loss.numel() * 4)
-            if self.training and self.dls is not None:
-                self._emit(self.fwd, "stp_scale_by_device", dl.data_ptr(), logits.rows * logits.gradC, self.cdt, self.dls.data_ptr(), self.dls.data_ptr() + 16)
+            self._emit_loss("stp_softmax_loss_ex", logits, target, (logits.rows, logits.C, logits.C), (w_cce, w_dice, w_iou, w_jaccard, w_focal))
             logits.grad_ready = self.training
             return
         self.loss_scalars = self._alloc((12,), torch.float32)
@@ -1461,12 +1456,7 @@ class Plan(object):
             logits.grad_ready = False
             logits.meta["fused_into_loss"] = True
             return
-        dl = self._gradbuf(logits) if self.training else None
-        self._emit(self.fwd, "stp_softmax_cce_dice", logits.buf.data_ptr(), target.buf.data_ptr(), logits.rows, logits.C, logits.C,
-                   self.cdt, float(w_cce), float(w_dice), self.loss_scalars.data_ptr(), dl.data_ptr() if dl is not None else None,
-                   logits.gradC, float(self.loss_scale), self.ws_loss.data_ptr(), self.ws_loss.numel() * 4)
-        if self.training and self.dls is not None:
-            self._emit(self.fwd, "stp_scale_by_device", dl.data_ptr(), logits.rows * logits.gradC, self.cdt, self.dls.data_ptr(), self.dls.data_ptr() + 16)
+        self._emit_loss("stp_softmax_cce_dice", logits, target, (logits.rows, logits.C, logits.C), (w_cce, w_dice))
         logits.grad_ready = self.training
 
     def softmax_out(self, logits):

@@ -157,12 +157,30 @@ def digest(text):
 
 
 # ------------------------------------------------------------------------------------------------ the matrix of DESIGN.md
-def _plan(net, backbone, size, batch, dtype, training=True, frozen=False, in_ch=3, **kw):
+class _HostLovaszSize(object):
+    """The library with the lovasz_loss sort-workspace query answered on the host (the library sizes it on a device; the launch
+    records hold the number, nothing else depends on it)."""
+
+    def __init__(self, lib):
+        self._lib = lib
+
+    def __getattr__(self, name):
+        return getattr(self._lib, name)
+
+    def stp_lovasz_workspace_bytes(self, count, images):
+        return 64 * int(count) + 4096 * int(images)
+
+
+def _plan(net, backbone, size, batch, dtype, training=True, frozen=False, in_ch=3, dynamic_loss_scale=False, **kw):
     def build():
         from segmentation_training_pipeline_amd import graph, nets
         plan = graph.Plan(batch, dtype, "cpu", training=training)
+        if len(kw.get("loss", ())) > 5 and kw["loss"][5]:
+            plan.lib = _HostLovaszSize(plan.lib)
         if dtype == "fp16":
             plan.loss_scale = 16384.0
+        if dynamic_loss_scale:      # the device record backend.HipSegModel gives an fp16 plan: stp_scale_by_device follows the loss
+            plan.dls = torch.zeros(8, dtype=torch.float32)
         if frozen:
             plan.frozen_prefixes = nets.ENCODER_PREFIXES
         classes = kw.get("classes", 1)
@@ -196,6 +214,11 @@ PLANS = {
     "unet_r34_256_inference_bf16": _plan("Unet", "resnet34", 256, 2, "bf16", training=False),
     "fpn_r50_256_fp16": _plan("FPN", "resnet50", 256, 4, "fp16", classes=3),
     "pspnet_r50_192_bf16": _plan("PSPNet", "resnet50", 192, 2, "bf16", classes=20),
+    # the loss heads no cell above reaches: the extended (iou / jaccard / focal) terms and lovasz_loss
+    "unet_r18_64_sigmoid_ex_bf16": _plan("Unet", "resnet18", 64, 2, "bf16", loss=(1.0, 0.5, 0.25, 0.125, 0.0625)),
+    "unet_r18_64_lovasz_bf16": _plan("Unet", "resnet18", 64, 2, "bf16", loss=(1.0, 1.0, 0.0, 0.0, 0.0, 0.5)),
+    "unet_r18_64_softmax3_ex_bf16": _plan("Unet", "resnet18", 64, 2, "bf16", classes=3, loss=(1.0, 0.5, 0.25, 0.125, 0.0625)),
+    "unet_r18_64_sigmoid_ex_fp16_dls": _plan("Unet", "resnet18", 64, 2, "fp16", loss=(1.0, 0.5, 0.25, 0.125, 0.0625), dynamic_loss_scale=True),
 }
 
 SWITCHES = [None, ("STP_HALO", "0"), ("STP_S2D", "0"), ("STP_SCATTER_1X1S2", "0"), ("STP_UPCOLLAPSE", "0"), ("STP_UPCOLLAPSE_BWD", "1"),

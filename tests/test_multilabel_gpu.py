@@ -125,7 +125,7 @@ def check(dtype, P, C, ldc, dlc, mix, target="random", seed=0, grad_scale=1.0):
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
 @pytest.mark.parametrize("C", [2, 3, 4, 5, 6, 7, 8])
-@pytest.mark.parametrize("P", [1, 255, 4097])
+@pytest.mark.parametrize("P", [1, 255, 4097, 50 * 1024 + 5])      # (the last: 50 value workgroups - the finalize reduction's prefetched loop and its remainder)
 def test_multilabel_loss_matches_reference(dtype, C, P):
     mix = ("bce", "bce+dice", "all")[(C + P) % 3]
     gsc = 1024.0 if dtype == "fp16" else 1.0                      # (IEEE half: the loss scale keeps 1/(P*C) gradients normal)

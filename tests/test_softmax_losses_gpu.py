@@ -140,7 +140,7 @@ def check(dtype, P, C, ldc, dlc, mix, target="random", seed=0, grad_scale=1.0):
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
 @pytest.mark.parametrize("C", CLASSES)
-@pytest.mark.parametrize("P", [1, 255, 4097])
+@pytest.mark.parametrize("P", [1, 255, 4097, 50 * 1024 + 5])      # (the last: 50 value workgroups - the finalize reduction's prefetched loop and its remainder)
 def test_softmax_loss_ex_matches_reference(dtype, C, P):
     mix = ("cce", "cce+dice", "all")[(C + P) % 3]
     gsc = 1024.0 if dtype == "fp16" else 1.0                      # (IEEE half: the loss scale keeps 1/(P*C) gradients normal)
