@@ -571,6 +571,29 @@ int stp_softmax_cce_dice_up(const void* low, const uint8_t* target, int32_t N, i
 /* probs [pixels][classes] fp32 = softmax of the first `classes` channels */
 int stp_softmax(const void* logits, float* probs, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype, void* stream);
 
+/* Confusion matrix of the multi-class head (metrics: categorical_accuracy, mean_iou, iou_class_k - K.argmax against the class-index
+ * target).  rows [pixels][ldc] in the storage type, logits or probabilities (only the first `classes` = 2..32 channels are read); target =
+ * class index per pixel, clamped to classes - 1 as the loss kernels clamp it.  Predicted class = the FIRST index of the row maximum of
+ * the stored values (numpy.argmax); it lies in [0, classes) whatever the values are, NaN included.  counts: dense [classes][classes]
+ * int32, counts[t * classes + p]; every call OVERWRITES it (no accumulation), nothing behind entry classes * classes is touched, the
+ * entries sum to `pixels`.  Integer sums: two calls and a graph replay give the same counts bit for bit.  pixels in 1 .. 2^31 - 1
+ * (argument 2, as in every loss launch: Plan.rerun_loss shortens it); workspace >= stp_class_confusion_workspace_bytes(classes)
+ * (0 for classes outside 2..32).  rows / low are 16-byte aligned, as every buffer of this interface: rows whose stride is a multiple of
+ * 16 bytes are read as 16-byte vectors without a check.
+ * _up: the same matrix for logits low [N][H][W][ldc] held at 1 / factor (2 / 4 / 8 / 16) of the mask's resolution, target
+ * [N][H factor][W factor]: each class is interpolated in fp32 with stp_resize_bilinear's expression and rounded to the storage type as
+ * its store rounds, so the counts EQUAL those of stp_resize_bilinear followed by stp_class_confusion (no tolerance).  _up_ok: 1 if the
+ * form serves (factor, classes, dtype).
+ * STP_E_BADARG: classes outside 2..32, ldc < classes, null pointers, pixels <= 0 or >= 2^31, an unsupported factor, the other build's
+ * 16-bit dtype; STP_E_WORKSPACE: less workspace than the query returns. */
+size_t stp_class_confusion_workspace_bytes(int32_t classes);
+int stp_class_confusion(const void* rows, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype,
+                        int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int stp_class_confusion_up_ok(int32_t factor, int32_t classes, int32_t dtype);
+int stp_class_confusion_up(const void* low, const uint8_t* target, int32_t N, int32_t H, int32_t W, int32_t factor,
+                           int32_t classes, int32_t ldc, int32_t dtype, int32_t* counts, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Optimizers over a flat fp32 arena (Keras 2.2.4 update rules, schemas/segmentation.raml:77-89).
  * `state` is a device int32[2]: [0] = iteration counter (incremented by the launch, so a captured

@@ -63,11 +63,41 @@ def parse_loss(spec, classes=1, architecture=None, activation=None):
     return w[ce], w["dice_loss"]
 
 
+CLASS_METRICS = ("categorical_accuracy", "mean_iou")      # + iou_class_0 .. iou_class_<classes - 1>: the softmax heads' confusion metrics
+
+
+def class_metric_names(classes):
+    return list(CLASS_METRICS) + ["iou_class_%d" % k for k in range(int(classes))]
+
+
+def is_class_metric(name):
+    """``name`` (with or without ``val_``) is one of the quantities that come from the confusion matrix."""
+    base = name[4:] if str(name).startswith("val_") else str(name)
+    return base in CLASS_METRICS or (base.startswith("iou_class_") and base[10:].isdigit())
+
+
+def confusion_metrics(matrix):
+    """[classes, classes] counts (target class, predicted class) -> categorical_accuracy = trace / total, iou_class_k =
+    M[k][k] / (row_k + col_k - M[k][k]) (0.0 when that union is empty) and mean_iou = their mean over the classes with a non-empty
+    union (the tf.metrics.mean_iou rule).  Exact integer sums; an all-zero matrix gives zeros."""
+    m = np.asarray(matrix, np.int64)
+    m = m.reshape(int(round(np.sqrt(m.size))), -1)
+    diag = np.diag(m)
+    union = m.sum(axis=1) + m.sum(axis=0) - diag
+    total = int(m.sum())
+    iou = [float(d) / float(u) if u > 0 else 0.0 for d, u in zip(diag, union)]
+    seen = int((union > 0).sum())
+    out = {"categorical_accuracy": float(diag.sum()) / total if total else 0.0,
+           "mean_iou": float(sum(iou)) / seen if seen else 0.0}
+    out.update(("iou_class_%d" % k, v) for k, v in enumerate(iou))
+    return out
+
+
 class HipSegModel(object):
     def __init__(self, architecture="Unet", backbone="resnet34", input_shape=(512, 512, 3), classes=1, activation="sigmoid",
                  batch=16, dtype="bf16", loss="binary_crossentropy", optimizer="Adam", lr=1e-3, freeze_encoder=False,
                  decoder_filters=(256, 128, 64, 32, 16), clipnorm=None, clipvalue=None, use_graph=True, device="cuda",
-                 opt_kwargs=None, seed=42, decoder_block_type="upsampling", net_kwargs=None, loss_scale=None):
+                 opt_kwargs=None, seed=42, decoder_block_type="upsampling", net_kwargs=None, loss_scale=None, class_metrics=False):
         if architecture not in nets.NETWORKS:
             raise ValueError("Unknown architecture")
         if backbone not in nets.known_backbones() or (backbone in nets.VGG_BLOCKS and architecture not in ("Unet", "Linknet", "FPN", "PSPNet")) \
@@ -84,6 +114,11 @@ class HipSegModel(object):
         # the head's activation ("sigmoid" for one class or multi-label, "softmax"); (`activation(name)` reads a plan tensor)
         self.head_activation = "softmax" if (classes > 1 and activation == "softmax") else "sigmoid"
         self.multilabel = is_multilabel(classes, activation)
+        # categorical_accuracy, mean_iou, iou_class_k from the confusion matrix the plan counts behind the loss launch (stp_class_confusion)
+        self.class_metrics = bool(class_metrics)
+        if self.class_metrics and self.head_activation != "softmax":
+            raise ValueError("class_metrics (categorical_accuracy, mean_iou, iou_class_k) need a softmax head of 2..32 classes; this is a %s "
+                             "sigmoid head" % ("multi-label" if self.multilabel else "one-class"))
         self.architecture, self.backbone = architecture, backbone
         self.H, self.W, self.in_ch = int(input_shape[0]), int(input_shape[1]), int(input_shape[2])
         self.classes, self.batch, self.dtype = classes, int(batch), dtype
@@ -111,7 +146,7 @@ class HipSegModel(object):
         self._segments = None
         self._works = []
         self._graphs = None
-        self.plan = graph.Plan(self.batch, dtype, device, training=True)
+        self.plan = graph.Plan(self.batch, dtype, device, training=True, class_metrics=self.class_metrics)
         # fp16 storage (BASELINE configs[3]): static loss scaling - the loss kernels seed the backward with loss_scale * dL/dlogits
         # (their grad_scale argument), every gradient in the arena is linear in it, and the optimizers' device scalar gscale
         # carries 1/loss_scale (times the data-parallel mean and the clipnorm factor).  2^14 keeps the 1/(N*H*W) BCE gradient
@@ -190,7 +225,7 @@ class HipSegModel(object):
     def eval_plan(self):
         """Inference-phase plan WITH the loss/metric reduction (validation pass of fit()); shares weights."""
         if getattr(self, "_eval", None) is None:
-            ep = graph.Plan(self.batch, self.dtype, str(self.device), training=False)
+            ep = graph.Plan(self.batch, self.dtype, str(self.device), training=False, class_metrics=self.class_metrics)
             ep.define(self._net(False, with_loss=True), share=self.plan)
             self._eval = ep
         return self._eval
@@ -549,7 +584,16 @@ class HipSegModel(object):
                 out["lovasz_loss"] = float(s[12])
             for k in self.unevaluated_terms:
                 out.pop(k, None)
+        if self.class_metrics:
+            out.update(confusion_metrics(self.confusion()))
         return out
+
+    def confusion(self, plan=None):
+        """int64 [classes, classes]: pixels of the last step by (target class, predicted class = first argmax of the head's output)."""
+        plan = plan or self.plan
+        if not self.class_metrics or plan.class_counts is None:
+            raise ValueError("the model was built without class_metrics")
+        return plan.class_counts.cpu().numpy().astype(np.int64).reshape(self.classes, self.classes)
 
     def logits(self):
         ts = self.plan.tensors                     # FPN / PSPNet / DeepLab: the head output is a resized tensor named "logits"

@@ -74,7 +74,7 @@ class ParamInfo(object):
 
 
 class Plan(object):
-    def __init__(self, batch, dtype="bf16", device="cuda", training=True):
+    def __init__(self, batch, dtype="bf16", device="cuda", training=True, class_metrics=False):
         if dtype not in _TD:
             raise ValueError("dtype must be 'bf16', 'fp16' or 'fp32'")
         self.device = torch.device(device)
@@ -166,6 +166,10 @@ class Plan(object):
         self._slot_used = 0
         self.slot_arena = None
         self.loss_scalars = None
+        # multi-class heads: one confusion launch (stp_class_confusion / _up) directly behind the loss launch writes class_counts,
+        # int32 [classes][classes] (target class, predicted class) - categorical_accuracy, mean_iou, iou_class_k.  Off: no launch
+        self.class_metrics = bool(class_metrics)
+        self.class_counts = None
         self.inputs = {}
 
     # ------------------------------------------------------------------ definition driver
@@ -1194,6 +1198,7 @@ class Plan(object):
             self._emit(self.fwd, "stp_prob_cce_dice", probs.buf.data_ptr(), target.buf.data_ptr(), probs.rows, probs.C, probs.C, self.cdt,
                        float(w_ce), float(w_dice), self.loss_scalars.data_ptr(), dp.data_ptr() if dp is not None else None, probs.gradC,
                        self.ws_loss.data_ptr(), self.ws_loss.numel() * 4)
+            self._emit_confusion(probs, target)       # (an argmax does not care whether the rows hold logits or probabilities)
         probs.grad_ready = self.training
 
     def probs_out(self, probs):
@@ -1373,6 +1378,24 @@ class Plan(object):
             self._emit(self.fwd, "stp_scale_by_device", dl.data_ptr(), logits.rows * logits.gradC, self.cdt, self.dls.data_ptr(), self.dls.data_ptr() + 16)
         return dl
 
+    def _emit_confusion(self, rows, target, factor=0):
+        """With ``class_metrics`` on: the confusion launch of a multi-class head into ``class_counts``.  ``rows``: the tensor the argmax
+        runs over - at the mask's resolution, or (``factor``) the logits held at 1 / factor of it (stp_class_confusion_up)."""
+        if not self.class_metrics:
+            return
+        classes = rows.C
+        nb = int(self.lib.stp_class_confusion_workspace_bytes(classes))
+        if nb <= 0:
+            raise StpShapeError("class metrics need a head of 2..32 classes")
+        self.class_counts = self._alloc((classes * classes,), torch.int32)
+        ws = self._alloc((nb // 4,), torch.int32)
+        if factor:
+            self._emit(self.fwd, "stp_class_confusion_up", rows.buf.data_ptr(), target.buf.data_ptr(), self.N, rows.H, rows.W, factor, classes,
+                       rows.C, self.cdt, self.class_counts.data_ptr(), ws.data_ptr(), nb)
+        else:
+            self._emit(self.fwd, "stp_class_confusion", rows.buf.data_ptr(), target.buf.data_ptr(), rows.rows, classes, rows.C, self.cdt,
+                       self.class_counts.data_ptr(), ws.data_ptr(), nb)
+
     def sigmoid_loss(self, logits, target, w_bce, w_dice, w_iou=0.0, w_jaccard=0.0, w_focal=0.0, w_lovasz=0.0):
         """sigmoid + w_bce*binary_crossentropy + w_dice*dice_loss [+ w*iou_loss + w*jaccard_loss + w*focal_loss + w*lovasz_loss,
         the rest of the registry at reference segmentation.py:15-22]; seeds the backward pass."""
@@ -1431,13 +1454,15 @@ class Plan(object):
             self.loss_scalars = self._alloc((16,), torch.float32)
             self.loss_scalars.zero_()
             self._emit_loss("stp_softmax_loss_ex", logits, target, (logits.rows, logits.C, logits.C), (w_cce, w_dice, w_iou, w_jaccard, w_focal))
+            self._emit_confusion(logits, target)
             logits.grad_ready = self.training
             return
         self.loss_scalars = self._alloc((12,), torch.float32)
         rec = logits.meta.get("resize_rec")
         if (self.training and rec is not None and self.fwd[rec[0]][2] == "stp_resize_bilinear" and rec[1].needs_grad
                 and not rec[1].grad_ready and target.buf.data_ptr() % 4 == 0
-                and self.lib.stp_softmax_cce_dice_up_ok(rec[2], logits.C, self.cdt)):
+                and self.lib.stp_softmax_cce_dice_up_ok(rec[2], logits.C, self.cdt)
+                and (not self.class_metrics or self.lib.stp_class_confusion_up_ok(rec[2], logits.C, self.cdt))):
             # the logits are a bilinear resize of the class convolution's output (PSPNet, FPN) and only this loss reads them: both loss passes
             # interpolate from the low-resolution tensor, the gradient pass reduces straight into its gradient - the resized logits, their
             # gradient, the resize launch, stp_scale_by_device and stp_resize_bilinear_bwd leave the step (the launch record is kept for
@@ -1452,11 +1477,13 @@ class Plan(object):
             self._emit(self.fwd, "stp_softmax_cce_dice_up", lo.buf.data_ptr(), target.buf.data_ptr(), self.N, lo.H, lo.W, f, logits.C, lo.C,
                        self.cdt, float(w_cce), float(w_dice), self.loss_scalars.data_ptr(), dlow.data_ptr(), lo.gradC, float(self.loss_scale),
                        dls, (dls + 16) if dls is not None else None, self.ws_loss.data_ptr(), self.ws_loss.numel() * 4, corners.data_ptr(), nb)
+            self._emit_confusion(lo, target, f)       # on the same low-resolution tensor: the resized logits stay out of the step
             lo.grad_ready = True
             logits.grad_ready = False
             logits.meta["fused_into_loss"] = True
             return
         self._emit_loss("stp_softmax_cce_dice", logits, target, (logits.rows, logits.C, logits.C), (w_cce, w_dice))
+        self._emit_confusion(logits, target)
         logits.grad_ready = self.training
 
     def softmax_out(self, logits):
@@ -1542,7 +1569,9 @@ class Plan(object):
         was filled by wrapping around: the duplicates must not enter val_loss / dice - Keras evaluates a short last batch
         as it is).  Samples are the slowest dimension of every tensor, so the real ones are a prefix of the element range.
         ``stp_lovasz_hinge`` ADDS its term to the scalars the first launch wrote, so it is re-run after it with
-        ``images = n_valid`` (its third argument)."""
+        ``images = n_valid`` (its third argument).  The confusion launch behind the loss (``class_metrics``) is re-run the same way
+        (``rerun_confusion``): its third argument is the pixel count (``stp_class_confusion``) or the image count (``_up``), and every
+        call overwrites the counts."""
         n_valid = int(n_valid)
         if not 0 < n_valid <= self.N:
             raise ValueError("n_valid out of range")
@@ -1560,6 +1589,20 @@ class Plan(object):
                 _lib.check(fn(*a, st), name)
         if not done:
             raise _lib.StpError("the plan has no loss launch")
+        self.rerun_confusion(n_valid)
+
+    def rerun_confusion(self, n_valid):
+        """Re-runs the confusion launch (``class_metrics``) over the first ``n_valid`` samples: ``class_counts`` then holds the real
+        samples of a padded batch alone.  It reads the head's output as the step left it; a plan without the launch does nothing."""
+        n_valid = int(n_valid)
+        if not 0 < n_valid <= self.N:
+            raise ValueError("n_valid out of range")
+        st = torch.cuda.current_stream().cuda_stream
+        for fn, args, name, _meta in self.fwd:
+            if name in ("stp_class_confusion", "stp_class_confusion_up"):
+                a = list(args)
+                a[2] = n_valid if name.endswith("_up") else args[2] // self.N * n_valid      # images / pixels
+                _lib.check(fn(*a, st), name)
 
     def _side_stream(self):
         if self._side is None:

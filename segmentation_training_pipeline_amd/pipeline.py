@@ -18,6 +18,7 @@ import torch
 import yaml
 
 from . import augment, distributed, ops
+from .backend import class_metric_names, confusion_metrics, is_class_metric
 
 # YAML keys flagged (meta.custom) in schemas/segmentation.raml:26-120 (+ the keys used by the examples that
 # the RAML does not list): consumed by the pipeline, never forwarded to the model constructor.
@@ -700,6 +701,10 @@ def _unlogged(model):
     return tuple(getattr(model, "unevaluated_terms", ()))
 
 
+def _class_metrics(model):
+    return bool(getattr(model, "class_metrics", False))
+
+
 class Trainer(object):
     def __init__(self, model, feeder, ds, callbacks, rank=0, world=1):
         self.model, self.feeder, self.ds, self.callbacks = model, feeder, ds, callbacks
@@ -728,6 +733,8 @@ class Trainer(object):
         m = self.model
         plan = m.plan if training else m.eval_plan()
         snaps, counts = [], []
+        # class metrics: the batches' confusion matrices are summed on the device in int64 and fetched once per epoch, like the scalars
+        conf = torch.zeros(m.classes * m.classes, dtype=torch.int64, device=plan.device) if _class_metrics(m) else None
         # Training: the NEXT batch's device passes (resize + augmentation kernels, ~60 us at 16 x 512 x 512) are issued on an auxiliary
         # stream as soon as this step's forward + backward has consumed the input buffers, and run next to the optimizer
         # (HBM-bound, ~100 us) instead of in front of the next forward.  OPT-IN (STP_FEED_OVERLAP=1): measured 0.03 ms SLOWER per step on
@@ -768,6 +775,10 @@ class Trainer(object):
             # the step's scalars stay on the device (no host sync per batch: the host keeps running ahead, so the next
             # batch's H2D copies overlap this step); they are fetched once per epoch
             snaps.append(plan.loss_scalars.clone())
+            if conf is not None:
+                if training and n_real < m.batch:      # a padded last training batch: its wrap-around duplicates are not counted
+                    plan.rerun_confusion(n_real)
+                conf += plan.class_counts
             counts.append(n_real)
             items = nxt
         sums = {}
@@ -775,28 +786,46 @@ class Trainer(object):
             for scal, n in zip(torch.stack(snaps).cpu().numpy(), counts):
                 for k, v in derived_metrics(scal, getattr(m, "classes", 1), _extended(m), _activation(m), _unlogged(m)).items():
                     sums[k] = sums.get(k, 0.0) + v * n
+        if conf is not None:
+            sums[CONFUSION_KEY] = conf.cpu().numpy()
         return sums, int(sum(counts))
 
     def run_epoch(self, indexes, training):
         """Sample-weighted epoch means, combined over all ranks (one small SUM-all-reduce per call): every rank returns
         the same values bit for bit."""
         sums, n = self.run_epoch_sums(indexes, training)
-        return reduce_epoch_sums(sums, n, getattr(self.model, "classes", 1), _extended(self.model), _activation(self.model), _unlogged(self.model))
+        return reduce_epoch_sums(sums, n, getattr(self.model, "classes", 1), _extended(self.model), _activation(self.model), _unlogged(self.model),
+                                 _class_metrics(self.model))
 
 
-def epoch_log_names(classes=1, extended=False, activation=None, unlogged=()):
-    return sorted(derived_metrics(np.zeros(16, np.float32), classes, extended, activation, unlogged))
+CONFUSION_KEY = "confusion"      # run_epoch_sums: the epoch's confusion matrix (int64 [classes * classes]) rides in the sums under this key
 
 
-def reduce_epoch_sums(sums, n, classes=1, extended=False, activation=None, unlogged=()):
+def epoch_log_names(classes=1, extended=False, activation=None, unlogged=(), class_metrics=False):
+    """``class_metrics``: the model counts the confusion matrix (HipSegModel.class_metrics): categorical_accuracy, mean_iou, iou_class_k."""
+    names = list(derived_metrics(np.zeros(16, np.float32), classes, extended, activation, unlogged))
+    return sorted(names + (class_metric_names(classes) if class_metrics else []))
+
+
+def reduce_epoch_sums(sums, n, classes=1, extended=False, activation=None, unlogged=(), class_metrics=False):
     """{name: weighted sum}, samples -> {name: mean over the samples of ALL ranks}.  The vector layout is fixed by the
-    metric names (not by what a rank happened to see), so a rank with an empty shard still takes part in the collective."""
+    metric names (not by what a rank happened to see), so a rank with an empty shard still takes part in the collective.
+    ``class_metrics``: the classes^2 entries of the epoch's confusion matrix follow the sample count (zeros from a rank that saw
+    nothing; integers below 2^53 are exact in the float64 vector); the class metrics are ratios of the SUMMED matrix, not means of
+    per-batch ratios."""
     names = epoch_log_names(classes, extended, activation, unlogged)
-    vec = distributed.allreduce_sums([sums.get(k, 0.0) for k in names] + [float(n)])
-    total = vec[-1]
+    vec = [sums.get(k, 0.0) for k in names] + [float(n)]
+    if class_metrics:
+        conf = sums.get(CONFUSION_KEY)
+        vec += [0.0] * (classes * classes) if conf is None else [float(v) for v in np.asarray(conf).reshape(-1)]
+    vec = distributed.allreduce_sums(vec)
+    total = vec[len(names)]
     if total <= 0:
         return {}
-    return {k: float(vec[i] / total) for i, k in enumerate(names)}
+    out = {k: float(vec[i] / total) for i, k in enumerate(names)}
+    if class_metrics:
+        out.update(confusion_metrics(np.rint(vec[len(names) + 1:]).astype(np.int64)))
+    return out
 
 
 # ------------------------------------------------------------------------------------------ config
@@ -916,10 +945,21 @@ class GenericTaskConfig(object):
             stage.unfreeze(model)
         rank, local_rank, world = distributed.env_world()
         device = "cuda:%d" % distributed.device_index(local_rank)
+        # (the switch is passed only where it is on: a compile() without the keyword keeps working for every other experiment)
+        extra = {"class_metrics": True} if self._wants_class_metrics(model, stage) else {}
         model.compile(optimizer=self.optimizer, loss=loss, lr=lr, batch=self.batch, dtype=self.dtype, clipnorm=self.clipnorm,
                       clipvalue=self.clipvalue, metrics=self.metrics, device=device, use_graph=use_graph,
-                      loss_scale=float(self.loss_scale) if self.loss_scale else None)
+                      loss_scale=float(self.loss_scale) if self.loss_scale else None, **extra)
         return model
+
+    def _wants_class_metrics(self, model, stage=None):
+        """A softmax head whose ``metrics:``, ``primary_metric`` or a callback's ``monitor`` names categorical_accuracy, mean_iou or
+        iou_class_k (with or without ``val_``) counts the confusion matrix; every other experiment is planned as it was."""
+        if not (getattr(model, "classes", 1) > 1 and getattr(model, "activation", None) == "softmax"):
+            return False
+        cbs = stage.callbacks() if stage is not None else make_callbacks(self.all.get("callbacks"))
+        named = list(self.metrics) + [self.primary_metric] + [cb.monitor for cb in cbs if hasattr(cb, "monitor")]
+        return any(is_class_metric(name) for name in named)
 
     def load_model(self, fold=0, stage=-1):
         if stage < 0:
@@ -1040,7 +1080,7 @@ class GenericTaskConfig(object):
         # primary_metric / callback monitors are checked against the names an epoch will log BEFORE the first epoch trains (a typo used
         # to surface only after a whole epoch: advisor finding, round 3)
         known = {}
-        for k in epoch_log_names(self.classes, _extended(impl), _activation(impl), _unlogged(impl)) + ["lr"]:
+        for k in epoch_log_names(self.classes, _extended(impl), _activation(impl), _unlogged(impl), _class_metrics(impl)) + ["lr"]:
             known[k] = 0.0
             known["val_" + k] = 0.0
         for what, name in [("primary_metric", self.primary_metric)] + [("%s.monitor" % type(cb).__name__, cb.monitor) for cb in cbs if hasattr(cb, "monitor")]:
