@@ -802,6 +802,30 @@ int stp_se_excite_bwd(const float* workspace, int32_t N, int64_t HW, int32_t C, 
 int stp_se_bwd_apply(const void* dx, void* du, int32_t dtype, int32_t N, int64_t HW, int32_t C, const float* s, const float* dz,
                      void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Prediction on the device (csrc/predict.hip): flip test-time augmentation, fold ensembling, the way back to the image's own size and
+ * the label map, on the fp32 probabilities an inference plan leaves on the device.  uint8 and fp32 only (both builds export the same
+ * code).  Each value comes from the operation numpy applies on the host - one fp32 add, one correctly rounded fp32 division, one fp32
+ * multiplication, a truncation - so the results equal the host chain of segmentation_pipeline/segmentation.py (predict_on_batch,
+ * _scale_back, `(x * 255).astype(uint8)`, argmax) bit for bit.  No atomics; element indices are int64.  16-byte accesses where the
+ * destination rows start on 16-byte boundaries (aligned base, row pitch a multiple of 16 bytes; stp_predict_finish ends such a row with
+ * a scalar tail), one element per thread otherwise.  STP_E_BADARG before any launch: a NULL pointer, a size (or k) <= 0, flip outside
+ * 0..2, mode outside 0..2, source == destination, out_ld < w, mode 2 with C > 32.
+ *
+ * flip: 0 = none, 1 = columns reversed (x[:, :, ::-1]), 2 = rows reversed (x[:, ::-1]); whole pixels move, channels keep their order.
+ *   stp_flip_u8            : dst[N][H][W][C] = flip(src) - a flipped batch written straight into an inference plan's image buffer.
+ *   stp_predict_accumulate : acc[N][H][W][C] += flip(probs) (the un-flip of a map predicted from a flipped input); the caller zeroes acc.
+ *   stp_predict_finish     : ONE image.  acc = that image's [H][W][C] sums, k = how many maps were added.  For y < h, x < w:
+ *                            value = acc[y * H / h][x * W / w][c] / (float)k (integer division of the coordinates: the nearest gather of
+ *                            _scale_back); rows of `out` lie out_ld PIXELS apart (>= w: a `crops` cell is written into its rectangle of
+ *                            the full map).  mode 0: out fp32 [h][w][C] = value;  1: out uint8 [h][w][C] = (uint8)(value * 255.f),
+ *                            truncating;  2: out uint8 [h][w] = the first index of the largest of the C values (numpy.argmax; 2 <= C <= 32;
+ *                            a NaN never wins) or, C == 1, value > 0.5f. */
+int stp_flip_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t C, int32_t flip, void* stream);
+int stp_predict_accumulate(const float* probs, float* acc, int32_t N, int32_t H, int32_t W, int32_t C, int32_t flip, void* stream);
+int stp_predict_finish(const float* acc, int32_t H, int32_t W, int32_t C, int32_t k, int32_t mode, void* out, int32_t h, int32_t w,
+                       int32_t out_ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

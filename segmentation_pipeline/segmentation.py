@@ -48,6 +48,11 @@ def ansemblePredictions(sourceFolder, folders, cb, data, weights=None):
         cb(f, sum(a * wi for a, wi in zip(arrs, w)) / float(sum(w)), data)
 
 
+def _impl(model):
+    """The compiled HIP model behind what ``load_model`` returns (a models.SegModel), or the HipSegModel itself."""
+    return model._need() if hasattr(model, "_need") else model
+
+
 class SegmentationStage(generic.Stage):
     def unfreeze(self, model):
         # reference :259-260 -> segmentation_models.utils.set_trainable(model): every layer trainable
@@ -165,12 +170,16 @@ class PipelineConfig(generic.GenericTaskConfig):
         folds = fold if isinstance(fold, (list, tuple)) else [fold]
         return [self.load_model(f, stage) for f in folds]
 
-    def _resize_to_net(self, impl, images):
-        """uint8 HxWxC images of any size -> uint8 [n, H, W, C] at the network shape (stp_augment_u8, identity + resize)."""
+    def _resize_to_net(self, impl, images, device=False):
+        """uint8 HxWxC images of any size -> uint8 [n, H, W, C] at the network shape (stp_augment_u8, identity + resize).
+        ``device=True``: every image is resized into its slot of ONE device batch [impl.batch, H, W, C], which is returned as it is
+        (the slots behind the n images are not written, and nothing reads them) - nothing comes back to the host."""
         from segmentation_training_pipeline_amd import ops
         import torch
         H, W, ch = impl.H, impl.W, impl.in_ch
-        xs = np.zeros((len(images), H, W, ch), np.uint8)
+        if device and len(images) > impl.batch:
+            raise ValueError("%d images do not fit a batch of %d" % (len(images), impl.batch))
+        xs = torch.empty((impl.batch if device else len(images), H, W, ch), dtype=torch.uint8, device=impl.device)
         for i, img in enumerate(images):
             img = np.asarray(img)
             if img.ndim == 2:
@@ -183,14 +192,13 @@ class PipelineConfig(generic.GenericTaskConfig):
             h, w = img.shape[:2]
             prm = torch.from_numpy(generic.augment.identity_batch(1, h, w, (H, W))).to(impl.device)
             src = torch.from_numpy(img).to(impl.device)
-            dst = torch.empty((1, H, W, ch), dtype=torch.uint8, device=impl.device)
-            ops.augment_u8(src, None, dst, None, prm, 1, h, w, H, W, ch)
-            xs[i] = dst[0].cpu().numpy()
-        return xs
+            ops.augment_u8(src, None, xs[i:i + 1], None, prm, 1, h, w, H, W, ch)
+        return xs if device else xs.cpu().numpy()
 
     def predict_on_batch(self, models, ttflips, xs):
         """Mean of the fold models' probabilities, optionally with flip test-time augmentation (README.md:519-534).
-        ``models``: one model or a list; ``xs``: uint8 [n, H, W, 3] at the network shape, n <= inference batch."""
+        ``models``: one model or a list; ``xs``: uint8 [n, H, W, 3] at the network shape, n <= inference batch.
+        Numpy in, numpy out: the host statement of what ``predict_on_batch_device`` + stp_predict_finish compute on the device."""
         models = models if isinstance(models, (list, tuple)) else [models]
         acc = np.zeros((len(xs),) + tuple(xs.shape[1:3]) + (self.classes,), np.float32)
         k = 0
@@ -201,6 +209,31 @@ class PipelineConfig(generic.GenericTaskConfig):
                 acc += m.predict(xs[:, ::-1])[:, ::-1]; k += 1
         return acc / k
 
+    def predict_on_batch_device(self, models, ttflips, xs_dev, n):
+        """``predict_on_batch`` without the host: ``xs_dev`` is a uint8 device tensor [batch, H, W, C] at the network shape whose first
+        ``n`` images count.  Returns ``(acc, k)``: the float32 device SUM [batch, H, W, classes] of the k probability maps (models in
+        order, each plain, then - ``ttflips`` - from the column-flipped and from the row-flipped input, un-flipped:
+        stp_predict_accumulate) - the same additions in the same order as the host loop, so ``acc[:n] / k`` is its result bit for bit.
+        ``acc`` is this config's one accumulator of that shape: it is zeroed and reused by the next call; stp_predict_finish turns an
+        image's slice into the finished map."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        impls = [_impl(m) for m in (models if isinstance(models, (list, tuple)) else [models])]
+        i0 = impls[0]
+        key = (str(i0.device), i0.batch, i0.H, i0.W, int(self.classes))
+        cache = self.__dict__.setdefault("_accumulators", {})
+        numel = int(np.prod(key[1:]))
+        if key not in cache:          # (stp_zero_bytes clears whole 16-byte words: the buffer is rounded up to them)
+            cache[key] = torch.empty(-(-numel // 4) * 4, dtype=torch.float32, device=i0.device)
+        ops.zero_bytes(cache[key], cache[key].numel() * 4)
+        acc = cache[key][:numel].view(key[1:])
+        k = 0
+        for impl in impls:
+            for flip in ((0, 1, 2) if ttflips else (0,)):
+                probs = impl.predict_device(xs_dev, n, flip)
+                ops.predict_accumulate(probs, acc, int(n), i0.H, i0.W, int(self.classes), flip); k += 1
+        return acc, k
+
     @staticmethod
     def _scale_back(p, h, w):
         """Prediction at the network shape -> original image size (nearest, like the reference's Scale of a map)."""
@@ -208,54 +241,105 @@ class PipelineConfig(generic.GenericTaskConfig):
         xx = (np.arange(w) * p.shape[1] // w)[None, :]
         return p[yy, xx]
 
-    def predict_on_directory(self, spath, fold=0, stage=0, limit=-1, batch_size=32, ttflips=False):
+    # what stp_predict_finish writes: float32 H x W x classes probabilities, their `* 255` bytes, or the uint8 H x W label map
+    PROBS, BYTES, LABELS = 0, 1, 2
+
+    @staticmethod
+    def _new_map(acc, mode, h, w):
+        import torch
+        shape = (h, w) if mode == PipelineConfig.LABELS else (h, w, acc.shape[-1])
+        return torch.empty(shape, dtype=torch.float32 if mode == PipelineConfig.PROBS else torch.uint8, device=acc.device)
+
+    def _predict_maps(self, models, ttflips, items, mode=0, original_size=True):
+        """The finished maps (numpy, ``mode``: PROBS / BYTES / LABELS) of up to one batch of items, at each item's own size (or, with
+        ``original_size=False`` and no ``crops``, at the network shape).  Resize, flips, the sum over models and flips, the mean, the
+        way back to the image's size and the quantisation all run on the device; the finished maps of a batch come back in one copy
+        when they share a size, one copy per item otherwise."""
+        from segmentation_training_pipeline_amd import ops
+        if self.crops:
+            return [self._predict_cells(models, ttflips, it.x, mode) for it in items]
+        impl0 = _impl(models[0])
+        H, W = impl0.H, impl0.W
+        acc, k = self.predict_on_batch_device(models, ttflips, self._resize_to_net(impl0, [it.x for it in items], device=True), len(items))
+        sizes = [tuple(it.x.shape[:2]) if original_size else (H, W) for it in items]
+        if len(set(sizes)) == 1:
+            h, w = sizes[0]
+            out = self._new_map(acc, mode, len(items) * h, w)
+            for i in range(len(items)):
+                ops.predict_finish(acc[i], H, W, acc.shape[-1], k, mode, out[i * h:(i + 1) * h], h, w)
+            return list(out.cpu().numpy().reshape((len(items), h) + tuple(out.shape[1:])))
+        maps = []
+        for i, (h, w) in enumerate(sizes):
+            out = self._new_map(acc, mode, h, w)
+            ops.predict_finish(acc[i], H, W, acc.shape[-1], k, mode, out, h, w)
+            maps.append(out.cpu().numpy())
+        return maps
+
+    def _predict_batches(self, spath, fold, stage, limit, ttflips, mode=0, original_size=True):
         from segmentation_pipeline.impl.datasets import DirectoryDataSet
         nets_ = self._models(fold, stage)
         ds = DirectoryDataSet(spath)
         n = len(ds) if limit < 0 else min(limit, len(ds))
-        impl0 = nets_[0].impl
-        B = impl0.batch
+        B = nets_[0].impl.batch
         for s in range(0, n, B):
             items = [ds[i] for i in range(s, min(s + B, n))]
-            if self.crops:
-                yield items, [self._predict_cells(nets_, ttflips, it.x) for it in items]
-                continue
-            xs = self._resize_to_net(impl0, [it.x for it in items])
-            yield items, self.predict_on_batch(nets_, ttflips, xs)
+            yield items, self._predict_maps(nets_, ttflips, items, mode, original_size)
 
-    def _predict_cells(self, models, ttflips, img):
+    def predict_on_directory(self, spath, fold=0, stage=0, limit=-1, batch_size=32, ttflips=False):
+        """Yields (items, probabilities) per batch: a float32 array [n, H, W, classes] at the network shape, or - ``crops`` - the
+        list of the items' assembled maps at their own sizes."""
+        for items, maps in self._predict_batches(spath, fold, stage, limit, ttflips, self.PROBS, original_size=False):
+            yield items, (maps if self.crops else np.stack(maps))
+
+    def _predict_cells(self, models, ttflips, img, mode=0):
         """``crops: N`` at prediction time (README.md:488-491): the image is split into the N x N cells the model was trained
-        on, every cell is predicted, scaled back to its own size and the map is assembled - invisible to the caller."""
+        on, every cell is predicted, scaled back to its own size and the map is assembled - invisible to the caller.  Each cell is
+        finished into its rectangle of the full-size device map (stp_predict_finish with the map's row pitch); one copy brings it back."""
+        from segmentation_training_pipeline_amd import ops
         from segmentation_training_pipeline_amd.pipeline import crop_bounds
         c = int(self.crops)
         h, w = img.shape[:2]
         ys, xs_ = crop_bounds(h, c), crop_bounds(w, c)
         cells = [img[ys[r]:ys[r + 1], xs_[q]:xs_[q + 1]] for r in range(c) for q in range(c)]
-        impl0 = models[0].impl
-        out = np.zeros((h, w, self.classes), np.float32)
+        impl0 = _impl(models[0])
+        out = None
         for s in range(0, len(cells), impl0.batch):
             chunk = cells[s:s + impl0.batch]
-            probs = self.predict_on_batch(models, ttflips, self._resize_to_net(impl0, chunk))
-            for k, (cell, p) in enumerate(zip(chunk, probs), start=s):
-                r, q = divmod(k, c)
-                out[ys[r]:ys[r + 1], xs_[q]:xs_[q + 1]] = self._scale_back(p, *cell.shape[:2])
-        return out
+            acc, k = self.predict_on_batch_device(models, ttflips, self._resize_to_net(impl0, chunk, device=True), len(chunk))
+            if out is None:
+                out = self._new_map(acc, mode, h, w)      # (the cells tile it: every pixel is written)
+            for j, cell in enumerate(chunk):
+                r, q = divmod(s + j, c)
+                ops.predict_finish(acc[j], impl0.H, impl0.W, acc.shape[-1], k, mode, out[ys[r]:ys[r + 1], xs_[q]:xs_[q + 1]],
+                                   cell.shape[0], cell.shape[1], out_ld=w)
+        return out.cpu().numpy()
 
-    def predict_to_directory(self, spath, tpath, fold=0, stage=0, limit=-1, batchSize=32, binaryArray=False, ttflips=False):
+    def predict_to_directory(self, spath, tpath, fold=0, stage=0, limit=-1, batchSize=32, binaryArray=False, ttflips=False, labelMap=False):
+        """Writes one prediction per image of ``spath`` into ``tpath``: ``<stem>.png`` = probability of channel 0 as bytes (a
+        multi-label head: ``<stem>_<c>.png`` per class), ``binaryArray``: ``<stem>.npy`` = float32 H x W x classes.
+        ``labelMap=True``: ``<stem>.png`` holds the class index per pixel - the first largest of a softmax head's averaged
+        probabilities, 0/1 (probability > 0.5) for a one-class head; a multi-label head has no single label per pixel (ValueError)."""
+        multilabel = self.classes > 1 and self.all.get("activation") == "sigmoid"      # (independent sigmoid maps, H x W x classes)
+        if labelMap and multilabel:
+            raise ValueError("labelMap needs one label per pixel: a multi-label sigmoid head (classes: %d, activation: sigmoid) has "
+                             "independent maps - write them with labelMap=False" % self.classes)
+        if labelMap and binaryArray:
+            raise ValueError("labelMap writes PNGs of class indices, binaryArray writes float32 arrays: choose one")
         os.makedirs(tpath, exist_ok=True)
         from PIL import Image
-        multilabel = self.classes > 1 and self.all.get("activation") == "sigmoid"      # (independent sigmoid maps, H x W x classes)
-        for items, probs in self.predict_on_directory(spath, fold=fold, stage=stage, limit=limit, batch_size=batchSize, ttflips=ttflips):
-            for it, p in zip(items, probs):
-                scaled = self._scale_back(p, *it.x.shape[:2])
+        mode = self.LABELS if labelMap else (self.PROBS if binaryArray else self.BYTES)
+        for items, maps in self._predict_batches(spath, fold, stage, limit, ttflips, mode):
+            for it, m in zip(items, maps):
                 stem = it.id[0:it.id.index(".")] if "." in it.id else it.id
                 if binaryArray:
-                    np.save(os.path.join(tpath, stem), scaled)
+                    np.save(os.path.join(tpath, stem), m)
+                elif labelMap:
+                    Image.fromarray(m).save(os.path.join(tpath, stem + ".png"))
                 elif multilabel:              # one PNG per class: <stem>_<c>.png
-                    for c in range(scaled.shape[2]):
-                        Image.fromarray((scaled[:, :, c] * 255).astype(np.uint8)).save(os.path.join(tpath, "%s_%d.png" % (stem, c)))
+                    for c in range(m.shape[2]):
+                        Image.fromarray(np.ascontiguousarray(m[:, :, c])).save(os.path.join(tpath, "%s_%d.png" % (stem, c)))
                 else:
-                    Image.fromarray((scaled[:, :, 0] * 255).astype(np.uint8)).save(os.path.join(tpath, stem + ".png"))
+                    Image.fromarray(np.ascontiguousarray(m[:, :, 0])).save(os.path.join(tpath, stem + ".png"))
 
     def predict_in_directory(self, spath, fold, stage, cb=None, data=None, limit=-1, batchSize=32, ttflips=False):
         """Calls ``cb(file_name, map, data)`` per image with ``map.arr`` = probabilities at the ORIGINAL image size
@@ -263,9 +347,9 @@ class PipelineConfig(generic.GenericTaskConfig):
         omits ``stage`` (``predict_in_directory(path, folds, cb, data)``): that call shape is accepted too."""
         if callable(stage):
             stage, cb, data = 0, stage, cb
-        for items, probs in self.predict_on_directory(spath, fold=fold, stage=stage, limit=limit, batch_size=batchSize, ttflips=ttflips):
-            for it, p in zip(items, probs):
-                cb(it.id, PredictedMap(self._scale_back(p, *it.x.shape[:2])), data)
+        for items, maps in self._predict_batches(spath, fold, stage, limit, ttflips):
+            for it, m in zip(items, maps):
+                cb(it.id, PredictedMap(m), data)
 
     def evaluateAll(self, ds, fold, stage=-1, negatives="real", ttflips=None):
         """Iterator over validation batches of ``fold`` (reference :158-191): each carries the original ``images``,
@@ -276,13 +360,10 @@ class PipelineConfig(generic.GenericTaskConfig):
         B = m.impl.batch
         for s in range(0, len(indexes), B):
             items = [ds[i] for i in indexes[s:s + B]]
-            if self.crops:
-                probs = [self._predict_cells([m], ttflips, it.x) for it in items]
-            else:
-                probs = self.predict_on_batch(m, ttflips, self._resize_to_net(m.impl, [it.x for it in items]))
+            maps = self._predict_maps([m], ttflips, items)
             yield EvalBatch(images=[it.x for it in items], data=[it.id for it in items],
                             segmentation_maps=[PredictedMap(np.asarray(it.y)) for it in items],
-                            predicted_maps_aug=[PredictedMap(self._scale_back(p, *it.x.shape[:2])) for it, p in zip(items, probs)])
+                            predicted_maps_aug=[PredictedMap(p) for p in maps])
 
 
 class PredictedMap(object):

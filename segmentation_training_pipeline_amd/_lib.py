@@ -209,6 +209,9 @@ SIGNATURES = {
     "stp_se_bwd_reduce": (i32, [vp, vp, i32, i32, i64, i32, vp, sz, vp]),
     "stp_se_excite_bwd": (i32, [vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "stp_se_bwd_apply": (i32, [vp, vp, i32, i32, i64, i32, vp, vp, vp]),
+    "stp_flip_u8": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "stp_predict_accumulate": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "stp_predict_finish": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp]),
 }
 
 _libs = {}          # storage format ("bf16" | "fp16") -> loaded library

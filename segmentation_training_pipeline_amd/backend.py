@@ -610,14 +610,17 @@ class HipSegModel(object):
         return float(self.lr.item())
 
     # ------------------------------------------------------------------ inference
-    def predict(self, x):
-        """``model.predict``: x uint8 [B,H,W,C] (any B) -> float32 probabilities [B,H,W,classes].
-        Inference-phase BatchNormalization (moving statistics), weights shared with training."""
+    def _infer_plan(self):
         if self._infer is None:
             ip = graph.Plan(self.batch, self.dtype, str(self.device), training=False)
             ip.define(self._net(False), share=self.plan)
             self._infer = ip
-        ip = self._infer
+        return self._infer
+
+    def predict(self, x):
+        """``model.predict``: x uint8 [B,H,W,C] (any B) -> float32 probabilities [B,H,W,classes].
+        Inference-phase BatchNormalization (moving statistics), weights shared with training."""
+        ip = self._infer_plan()
         x = np.ascontiguousarray(x)
         if x.dtype != np.uint8:
             raise TypeError("images must be uint8 (raw 0..255)")
@@ -633,3 +636,19 @@ class HipSegModel(object):
             ip.run(ip.prep); ip.run(ip.fwd)
             out[s:s + n] = ip.probs[:n].cpu().numpy()
         return out
+
+    def predict_device(self, x_dev, n, flip=0):
+        """``predict`` without the host: ``x_dev`` is a uint8 device tensor [batch, H, W, C] whose first ``n`` images count; they go
+        into the inference plan's input flipped by ``flip`` (stp_flip_u8: 0 none, 1 columns reversed, 2 rows reversed), then the
+        weight copies and the forward pass run.  Returns the plan's float32 probabilities [batch, H, W, classes] ON THE DEVICE
+        (``[:n]`` are the batch's; not un-flipped), valid until the next ``predict`` / ``predict_device`` of this model."""
+        from . import ops
+        ip = self._infer_plan()
+        xi = ip.inputs["image"].buf
+        if not isinstance(x_dev, torch.Tensor) or x_dev.dtype != torch.uint8 or x_dev.device != xi.device or not x_dev.is_contiguous():
+            raise TypeError("predict_device takes a contiguous uint8 tensor on the model's device")
+        if tuple(x_dev.shape) != (self.batch, self.H, self.W, self.in_ch) or not 1 <= int(n) <= self.batch:
+            raise ValueError("predict_device takes [%d, %d, %d, %d] images and 1 <= n <= %d" % (self.batch, self.H, self.W, self.in_ch, self.batch))
+        ops.flip_u8(x_dev, xi, int(n), self.H, self.W, self.in_ch, flip)
+        ip.run(ip.prep); ip.run(ip.fwd)
+        return ip.probs

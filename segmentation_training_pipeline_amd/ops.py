@@ -354,3 +354,29 @@ def cast_f32_to_bf16(src, dst, count):
 
 def cast_bf16_to_f32(src, dst, count, scale=1.0):
     _lib.call("stp_cast_bf16_to_f32", ptr(src), ptr(dst), count, float(scale), stream())
+
+
+# prediction on the device (csrc/predict.hip): flip 0 none, 1 columns reversed, 2 rows reversed; uint8 images, fp32 probabilities
+def flip_u8(src, dst, N, H, W, Cn, flip):
+    if min(src.numel(), dst.numel()) < N * H * W * Cn:
+        raise ValueError("flip_u8: buffers are smaller than N x H x W x C")
+    _lib.call("stp_flip_u8", ptr(_dev(src)), ptr(_dev(dst)), N, H, W, Cn, int(flip), stream())
+
+
+def predict_accumulate(probs, acc, N, H, W, Cn, flip):
+    if min(probs.numel(), acc.numel()) < N * H * W * Cn:
+        raise ValueError("predict_accumulate: buffers are smaller than N x H x W x C")
+    _lib.call("stp_predict_accumulate", ptr(_dev(probs)), ptr(_dev(acc)), N, H, W, Cn, int(flip), stream())
+
+
+def predict_finish(acc, H, W, Cn, k, mode, out, h, w, out_ld=None):
+    """``acc``: ONE image's [H, W, Cn] sums; ``out``: fp32 (mode 0) or uint8 (1: bytes, 2: labels) whose first element is the map's
+    top-left corner - a view into a larger map with ``out_ld`` pixels per row writes a rectangle of it."""
+    out_ld = w if out_ld is None else int(out_ld)
+    per_px = 1 if mode == 2 else Cn
+    room = out.untyped_storage().nbytes() // out.element_size() - out.storage_offset()      # elements from the corner to the storage's end
+    if acc.numel() < H * W * Cn or (out_ld >= w and room < ((h - 1) * out_ld + w) * per_px):
+        raise ValueError("predict_finish: buffers are smaller than the maps")
+    if mode in (0, 1, 2) and out.dtype != (torch.float32 if mode == 0 else torch.uint8):
+        raise ValueError("predict_finish: mode %d writes %s" % (mode, "float32" if mode == 0 else "uint8"))
+    _lib.call("stp_predict_finish", ptr(_dev(acc)), H, W, Cn, int(k), int(mode), ptr(_dev(out)), h, w, out_ld, stream())
