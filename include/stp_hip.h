@@ -553,6 +553,32 @@ int stp_softmax_cce_dice(const void* logits, const uint8_t* target, int64_t pixe
 int stp_softmax_loss_ex(const void* logits, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc,
                         int32_t dtype, const float* weights5, float* scalars, void* dlogits, int32_t dl_channels,
                         float grad_scale, void* workspace, size_t workspace_bytes, void* stream);
+/* stp_softmax_loss_ex with an ignore label and class weights (experiment keys ignore_label / class_weights).  The arguments of
+ * stp_softmax_loss_ex, then ignore_label (-1: none, else 0..255: a pixel whose STORED target equals it takes no part in the loss, the
+ * gradient or the metrics) and class_weights (DEVICE pointer to `classes` floats, NULL: all 1; positive and finite - the host checks
+ * them, the kernel cannot).  The arithmetic, fixed HERE (the reference pins none):
+ *   t_i the stored target, v_i = [t_i != ignore_label]; the class of a counted pixel is min(t_i, classes - 1); w_c the class weights;
+ *   omega_i = v_i w_class(i); n = sum_i v_i, counted on the device (it differs from batch to batch); p = softmax(z), y the one-hot target.
+ *   1. per-pixel means (Keras's class_weight / zero sample weight rule: the weight multiplies the per-sample loss, the mean runs over
+ *      the samples that count):  categorical_crossentropy = sum_i omega_i ce_i / n,  jaccard_loss = sum_i omega_i jac_i / n,
+ *      focal_loss = sum_i omega_i sum_c focal_ic / (n classes) - ce_i, jac_i, focal_ic the per-pixel expressions of stp_softmax_loss_ex,
+ *      clips included.
+ *   2. region overlaps: dice_loss, iou_loss and the logged dice, iou, iot, binary_accuracy from sums over the counted pixels only
+ *      (sum_p, sum_y = n, sum_py and the thresholded sums each times v_i; accuracy over n classes elements); class weights do not enter.
+ *   3. loss = the weighted sum of the five terms (weights5).
+ *   4. n == 0: the three means are 0 (the divisor is max(n, 1)), the overlap terms take their smooth-term values (dice_loss 0, iou 1),
+ *      every gradient element is 0; nothing is NaN.
+ *   5. dlogits = the exact derivative of the above through the softmax x grad_scale; the row of an ignored pixel is exactly 0.0 in
+ *      every channel and IS stored, padding channels of every row are exactly 0; the 1e-7 clips pass no gradient.
+ *   6. ignore_label -1 and weights of 1 (or NULL): the scalars and gradients of stp_softmax_loss_ex on the same inputs.
+ * scalars (fp32[14]): [0..11] as stp_softmax_loss_ex ([11] = 0 when focal_loss has no weight), [12] = n, [13] = sum_i omega_i (n is exact
+ * in its float up to 2^24 counted pixels; the gradient pass reads it from there).  Deterministic: fixed-order reduction, no atomics.
+ * STP_E_BADARG as stp_softmax_loss_ex, and for ignore_label outside -1..255; STP_E_WORKSPACE below stp_loss_workspace_bytes().
+ * Not here: a fused low-resolution (_up) form, class weights on dice_loss / iou_loss, lovasz_loss. */
+int stp_softmax_loss_masked(const void* logits, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc,
+                            int32_t dtype, const float* weights5, float* scalars, void* dlogits, int32_t dl_channels,
+                            float grad_scale, void* workspace, size_t workspace_bytes, int32_t ignore_label,
+                            const float* class_weights, void* stream);
 /* The same loss on class logits the network produces at 1 / factor of the mask's resolution and resizes bilinearly (segmentation_models
  * 0.2.1: PSPNet `final_interpolation: bilinear` x downsample_factor, schemas/segmentation.raml:225-249; FPN's last UpSampling2D(4,
  * 'bilinear')) - replaces, in the training step, stp_resize_bilinear of the logits + stp_softmax_cce_dice + stp_scale_by_device +
@@ -584,11 +610,15 @@ int stp_softmax(const void* logits, float* probs, int64_t pixels, int32_t classe
  * [N][H factor][W factor]: each class is interpolated in fp32 with stp_resize_bilinear's expression and rounded to the storage type as
  * its store rounds, so the counts EQUAL those of stp_resize_bilinear followed by stp_class_confusion (no tolerance).  _up_ok: 1 if the
  * form serves (factor, classes, dtype).
- * STP_E_BADARG: classes outside 2..32, ldc < classes, null pointers, pixels <= 0 or >= 2^31, an unsupported factor, the other build's
+ * _ignore: stp_class_confusion with an ignore label (-1: none, else 0..255): pixels whose stored target equals it are not counted, the
+ * entries sum to the number of counted pixels; with -1 the counts are stp_class_confusion's.
+ * STP_E_BADARG: classes outside 2..32, ldc < classes, null pointers, pixels <= 0 or >= 2^31, an unsupported factor, ignore_label outside -1..255, the other build's
  * 16-bit dtype; STP_E_WORKSPACE: less workspace than the query returns. */
 size_t stp_class_confusion_workspace_bytes(int32_t classes);
 int stp_class_confusion(const void* rows, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype,
                         int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int stp_class_confusion_ignore(const void* rows, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype,
+                               int32_t* counts, void* workspace, size_t workspace_bytes, int32_t ignore_label, void* stream);
 int stp_class_confusion_up_ok(int32_t factor, int32_t classes, int32_t dtype);
 int stp_class_confusion_up(const void* low, const uint8_t* target, int32_t N, int32_t H, int32_t W, int32_t factor,
                            int32_t classes, int32_t ldc, int32_t dtype, int32_t* counts, void* workspace,

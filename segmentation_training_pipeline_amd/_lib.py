@@ -156,6 +156,7 @@ SIGNATURES = {
     "stp_sigmoid_multilabel_loss": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, i32, f32, vp, sz, vp]),
     "stp_sigmoid_multilabel_bias_grad": (i32, [vp, i64, i32, vp, i32, vp]),
     "stp_softmax_loss_ex": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, i32, f32, vp, sz, vp]),
+    "stp_softmax_loss_masked": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, i32, f32, vp, sz, i32, vp, vp]),
     "stp_lovasz_workspace_bytes": (sz, [i64, i32]),
     "stp_lovasz_hinge": (i32, [vp, vp, i32, i64, i32, f32, vp, vp, i32, vp, sz, vp]),
     "stp_sigmoid": (i32, [vp, vp, i64, i32, vp]),
@@ -166,6 +167,7 @@ SIGNATURES = {
     "stp_softmax": (i32, [vp, vp, i64, i32, i32, i32, vp]),
     "stp_class_confusion_workspace_bytes": (sz, [i32]),
     "stp_class_confusion": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, sz, vp]),
+    "stp_class_confusion_ignore": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, sz, i32, vp]),
     "stp_class_confusion_up_ok": (i32, [i32, i32, i32]),
     "stp_class_confusion_up": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
     "stp_adam": (i32, [vp, vp, vp, vp, i64, vp, f32, f32, f32, vp, vp, vp, f32, vp]),

@@ -93,11 +93,39 @@ def confusion_metrics(matrix):
     return out
 
 
+def check_masked_loss(ignore_label, class_weights, classes, architecture, head_activation, multilabel=False):
+    """The ``ignore_label`` / ``class_weights`` keys of a softmax head -> (int 0..255 or None, tuple of floats or None); ValueError for
+    what the backend cannot train that way."""
+    if ignore_label is None and class_weights is None:
+        return None, None
+    what = " / ".join(k for k, v in (("ignore_label", ignore_label), ("class_weights", class_weights)) if v is not None)
+    if head_activation != "softmax":
+        raise ValueError("%s needs a softmax head of 2..32 classes; this is a %s sigmoid head (its masks are {0,1} or 0/255, where 255 "
+                         "already means 1)" % (what, "multi-label" if multilabel else "one-class"))
+    if architecture == "DeepLabV3":
+        raise ValueError("%s is not available for DeepLabV3 (its loss runs on probabilities): use Unet, Linknet, FPN or PSPNet" % what)
+    if ignore_label is not None:
+        if isinstance(ignore_label, bool) or not isinstance(ignore_label, (int, np.integer)) or not 0 <= int(ignore_label) <= 255:
+            raise ValueError("ignore_label must be an integer 0..255 (the value of the void pixels in the label image), not %r" % (ignore_label,))
+        ignore_label = int(ignore_label)
+    if class_weights is not None:
+        try:
+            class_weights = tuple(float(w) for w in class_weights)
+        except TypeError:
+            raise ValueError("class_weights must be a list of one float per class, not %r" % (class_weights,))
+        if len(class_weights) != int(classes):
+            raise ValueError("class_weights has %d entries, the head has %d classes" % (len(class_weights), int(classes)))
+        if not all(np.isfinite(w) and w > 0 for w in class_weights):
+            raise ValueError("class_weights must be finite and > 0, got %r" % (class_weights,))
+    return ignore_label, class_weights
+
+
 class HipSegModel(object):
     def __init__(self, architecture="Unet", backbone="resnet34", input_shape=(512, 512, 3), classes=1, activation="sigmoid",
                  batch=16, dtype="bf16", loss="binary_crossentropy", optimizer="Adam", lr=1e-3, freeze_encoder=False,
                  decoder_filters=(256, 128, 64, 32, 16), clipnorm=None, clipvalue=None, use_graph=True, device="cuda",
-                 opt_kwargs=None, seed=42, decoder_block_type="upsampling", net_kwargs=None, loss_scale=None, class_metrics=False):
+                 opt_kwargs=None, seed=42, decoder_block_type="upsampling", net_kwargs=None, loss_scale=None, class_metrics=False,
+                 ignore_label=None, class_weights=None):
         if architecture not in nets.NETWORKS:
             raise ValueError("Unknown architecture")
         if backbone not in nets.known_backbones() or (backbone in nets.VGG_BLOCKS and architecture not in ("Unet", "Linknet", "FPN", "PSPNet")) \
@@ -119,6 +147,10 @@ class HipSegModel(object):
         if self.class_metrics and self.head_activation != "softmax":
             raise ValueError("class_metrics (categorical_accuracy, mean_iou, iou_class_k) need a softmax head of 2..32 classes; this is a %s "
                              "sigmoid head" % ("multi-label" if self.multilabel else "one-class"))
+        # ignore_label / class_weights (softmax heads of Unet / Linknet / FPN / PSPNet): stp_softmax_loss_masked, checked before any device work
+        self.ignore_label, self.class_weights = check_masked_loss(ignore_label, class_weights, classes, architecture, self.head_activation,
+                                                                  self.multilabel)
+        self.masked = self.ignore_label is not None or self.class_weights is not None
         self.architecture, self.backbone = architecture, backbone
         self.H, self.W, self.in_ch = int(input_shape[0]), int(input_shape[1]), int(input_shape[2])
         self.classes, self.batch, self.dtype = classes, int(batch), dtype
@@ -163,6 +195,7 @@ class HipSegModel(object):
         if self.loss_scale <= 0:
             raise ValueError("loss_scale must be positive")
         self.plan.loss_scale = self.loss_scale
+        self.plan.masked_loss = self._masked_loss()
         # DYNAMIC re-scaling on top of the static scale (fp16 only; STP_DYNAMIC_LOSS_SCALE=0 keeps the static scale + skip-on-overflow of
         # round 3): a device multiplier m (float[8] record, include/stp_hip.h) applied to the loss gradient right after the loss kernel,
         # halved when a step is skipped, doubled after `interval` clean steps - all inside the captured step.
@@ -222,10 +255,14 @@ class HipSegModel(object):
             return logits
         return fn
 
+    def _masked_loss(self):
+        return {"ignore_label": self.ignore_label, "class_weights": self.class_weights} if self.masked else None
+
     def eval_plan(self):
         """Inference-phase plan WITH the loss/metric reduction (validation pass of fit()); shares weights."""
         if getattr(self, "_eval", None) is None:
             ep = graph.Plan(self.batch, self.dtype, str(self.device), training=False, class_metrics=self.class_metrics)
+            ep.masked_loss = self._masked_loss()
             ep.define(self._net(False, with_loss=True), share=self.plan)
             self._eval = ep
         return self._eval
@@ -584,6 +621,8 @@ class HipSegModel(object):
                 out["lovasz_loss"] = float(s[12])
             for k in self.unevaluated_terms:
                 out.pop(k, None)
+        if self.masked:
+            out["counted_pixels"] = float(s[12])      # n of stp_softmax_loss_masked: the pixels of the batch that are not ignore_label
         if self.class_metrics:
             out.update(confusion_metrics(self.confusion()))
         return out

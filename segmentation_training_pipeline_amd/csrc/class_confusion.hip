@@ -2,6 +2,7 @@
 // the FIRST index of the row maximum of the stored values (K.argmax / numpy.argmax; logits or DeepLab's probabilities alike).
 // categorical_accuracy and the per-class / mean IoU of an epoch are ratios of sums of these integers (backend.confusion_metrics).
 //   stp_class_confusion     rows [pixels][ldc] at the mask's resolution
+//   stp_class_confusion_ignore  the same with an ignore label: pixels whose target holds it are not counted
 //   stp_class_confusion_up  logits held at 1 / f of it (where stp_softmax_cce_dice_up removed the resized tensor from the step): every output
 //                           pixel is interpolated with the expression of resize_bilinear_kernel (bn_pool.hip) and rounded to the storage
 //                           type as that kernel's store rounds it - the counts are those of stp_resize_bilinear + stp_class_confusion.
@@ -70,6 +71,35 @@ __global__ __launch_bounds__(CONF_THREADS) void class_confusion_kernel(const T* 
       class_row_load<T, CM>(rows + i * ldc, classes, vec, p, vec4);
       const int t = target[i] < classes ? target[i] : classes - 1;
       key = t * classes + first_argmax<CM>(p, classes);
+    }
+    wave_count(table, key);
+  }
+  conf_table_store<CONF_THREADS>(table, classes * classes, partial);
+}
+
+// class_confusion_kernel with an ignore label (stp_class_confusion_ignore): a pixel whose stored target equals it keeps key -1 - it
+// joins no key group of the ballot peel and adds nothing, so the table's total is the number of counted pixels.  A kernel of its own:
+// the instances of class_confusion_kernel stay as they were compiled.
+template <typename T, int CM>
+__global__ __launch_bounds__(CONF_THREADS) void class_confusion_ignore_kernel(const T* __restrict__ rows, const uint8_t* __restrict__ target,
+                                                                              int64_t pixels, int classes, int ldc, int ignore_label,
+                                                                              int* __restrict__ partial) {
+  __shared__ int table[STP_MAX_CLASSES * STP_MAX_CLASSES];
+  conf_table_clear<CONF_THREADS>(table, classes * classes);
+  const bool vec = (ldc % Elem<T>::VEC) == 0 && CM % Elem<T>::VEC == 0;
+  const bool vec4 = !vec && sizeof(T) == 2 && (ldc % 4) == 0 && (CM % 4) == 0 && !(reinterpret_cast<uintptr_t>(rows) & 7);
+  // (the trip count is the same in every lane of a wave: wave_count is called by all 64)
+  for (int64_t base = (int64_t)blockIdx.x * CONF_THREADS; base < pixels; base += (int64_t)gridDim.x * CONF_THREADS) {
+    const int64_t i = base + threadIdx.x;
+    int key = -1;
+    if (i < pixels) {
+      const int tr = target[i];
+      if (tr != ignore_label) {
+        float p[CM];
+        class_row_load<T, CM>(rows + i * ldc, classes, vec, p, vec4);
+        const int t = tr < classes ? tr : classes - 1;
+        key = t * classes + first_argmax<CM>(p, classes);
+      }
     }
     wave_count(table, key);
   }
@@ -183,6 +213,29 @@ extern "C" int stp_class_confusion(const void* rows, const uint8_t* target, int6
     loss_by_class_bucket(classes, [&](auto bucket) {
       constexpr int CM = decltype(bucket)::value;
       hipLaunchKernelGGL((class_confusion_kernel<T, CM>), dim3(blocks), dim3(CONF_THREADS), 0, s, (const T*)rows, target, pixels, classes, ldc, partial);
+    });
+  });
+  conf_finalize(partial, blocks, classes, counts, s);
+  STP_LAUNCH_CHECK();
+  return STP_OK;
+}
+
+extern "C" int stp_class_confusion_ignore(const void* rows, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype,
+                                          int32_t* counts, void* workspace, size_t workspace_bytes, int32_t ignore_label, void* stream) {
+  const int rc = loss_check(dtype, rows && target && counts && workspace && pixels > 0 && pixels < (1ll << 31) && classes >= 2 &&
+                                       classes <= STP_MAX_CLASSES && ldc >= classes && ignore_label >= -1 && ignore_label <= 255,
+                            workspace_bytes, classes >= 2 && classes <= STP_MAX_CLASSES ? conf_workspace_bytes(classes) : 0);
+  if (rc != STP_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t want = (pixels + CONF_THREADS - 1) / CONF_THREADS;
+  const int blocks = (int)(want > CONF_MAX_BLOCKS ? CONF_MAX_BLOCKS : want);
+  int* partial = (int*)workspace;
+  loss_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    loss_by_class_bucket(classes, [&](auto bucket) {
+      constexpr int CM = decltype(bucket)::value;
+      hipLaunchKernelGGL((class_confusion_ignore_kernel<T, CM>), dim3(blocks), dim3(CONF_THREADS), 0, s, (const T*)rows, target, pixels, classes, ldc,
+                         ignore_label, partial);
     });
   });
   conf_finalize(partial, blocks, classes, counts, s);

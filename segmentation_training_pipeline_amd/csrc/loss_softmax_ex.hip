@@ -16,27 +16,6 @@
 
 #define SMX_NSUM 16
 #define SMX_GRAD_MAX_BLOCKS 4096
-#define SMX_JACCARD_SMOOTH 100.f
-#define SMX_FOCAL_ALPHA 0.25f
-
-// 1 - p_c without cancellation: at most one probability of a row exceeds 0.5 - for the largest one (index *imax) 1 - p is the sum of
-// the OTHERS (returned), for every other class 1 - p_c >= 0.5 is exact enough as written.  A confidently wrong pixel (a class that is not
-// the target at p -> 1) is where focal_loss is largest: log(1 - p) and 1 / (1 - p) of a rounded 1.f - p lose 1e-7 / (1 - p) there.
-template <int CM>
-__device__ __forceinline__ float smx_rest(const float (&p)[CM], int* imax) {
-  float pmax = p[0], rest = 0.f;
-  int im = 0;
-#pragma unroll
-  for (int c = 1; c < CM; ++c) {
-    const bool gt = p[c] > pmax;
-    pmax = gt ? p[c] : pmax;
-    im = gt ? c : im;
-  }
-#pragma unroll
-  for (int c = 0; c < CM; ++c) rest += c == im ? 0.f : p[c];                 // (p[c] = 0 beyond `classes`)
-  *imax = im;
-  return rest;
-}
 
 // value pass: per-workgroup partials of
 //   0 cce_pixel  1 p  2 y (= 1 per pixel)  3 p_t  4 [pmax>.5]  5 [p_t>.5]  6 count of th == y  7 jaccard_pixel  8 focal_e   (9..15 zero)

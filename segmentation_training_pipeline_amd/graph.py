@@ -169,6 +169,10 @@ class Plan(object):
         # multi-class heads: one confusion launch (stp_class_confusion / _up) directly behind the loss launch writes class_counts,
         # int32 [classes][classes] (target class, predicted class) - categorical_accuracy, mean_iou, iou_class_k.  Off: no launch
         self.class_metrics = bool(class_metrics)
+        # the softmax head's ignore label / class weights: {"ignore_label": .., "class_weights": ..} read by softmax_loss (set before
+        # define, as loss_scale is), and the device tensor of the weights that launch reads
+        self.masked_loss = None
+        self.class_weights = None
         self.class_counts = None
         self.inputs = {}
 
@@ -1361,10 +1365,10 @@ class Plan(object):
             self._tape.append(back)
         return out
 
-    def _emit_loss(self, name, logits, target, dims, weights):
+    def _emit_loss(self, name, logits, target, dims, weights, tail=()):
         """The tail the loss launches on logits share: the gradient buffer (None outside training), the weights (two floats, or the
-        registry's five as a host array), `... gradC, loss_scale, workspace`, then the dynamic loss-scale multiplier.  Returns the
-        gradient buffer."""
+        registry's five as a host array), `... gradC, loss_scale, workspace` [, ``tail``: the arguments an entry takes behind its
+        workspace], then the dynamic loss-scale multiplier.  Returns the gradient buffer."""
         dl = self._gradbuf(logits) if self.training else None
         if len(weights) == 5:
             self._loss_weights = (C.c_float * 5)(*weights)     # host array read at launch
@@ -1373,14 +1377,15 @@ class Plan(object):
             weights = tuple(float(w) for w in weights)
         self._emit(self.fwd, name, logits.buf.data_ptr(), target.buf.data_ptr(), *dims, self.cdt, *weights, self.loss_scalars.data_ptr(),
                    dl.data_ptr() if dl is not None else None, logits.gradC, float(self.loss_scale), self.ws_loss.data_ptr(),
-                   self.ws_loss.numel() * 4)
+                   self.ws_loss.numel() * 4, *tail)
         if self.training and self.dls is not None:
             self._emit(self.fwd, "stp_scale_by_device", dl.data_ptr(), logits.rows * logits.gradC, self.cdt, self.dls.data_ptr(), self.dls.data_ptr() + 16)
         return dl
 
-    def _emit_confusion(self, rows, target, factor=0):
+    def _emit_confusion(self, rows, target, factor=0, ignore_label=None):
         """With ``class_metrics`` on: the confusion launch of a multi-class head into ``class_counts``.  ``rows``: the tensor the argmax
-        runs over - at the mask's resolution, or (``factor``) the logits held at 1 / factor of it (stp_class_confusion_up)."""
+        runs over - at the mask's resolution, or (``factor``) the logits held at 1 / factor of it (stp_class_confusion_up).
+        ``ignore_label`` (not None: the masked loss, -1 = class weights alone): stp_class_confusion_ignore, full resolution only."""
         if not self.class_metrics:
             return
         classes = rows.C
@@ -1392,6 +1397,9 @@ class Plan(object):
         if factor:
             self._emit(self.fwd, "stp_class_confusion_up", rows.buf.data_ptr(), target.buf.data_ptr(), self.N, rows.H, rows.W, factor, classes,
                        rows.C, self.cdt, self.class_counts.data_ptr(), ws.data_ptr(), nb)
+        elif ignore_label is not None:
+            self._emit(self.fwd, "stp_class_confusion_ignore", rows.buf.data_ptr(), target.buf.data_ptr(), rows.rows, classes, rows.C, self.cdt,
+                       self.class_counts.data_ptr(), ws.data_ptr(), nb, int(ignore_label))
         else:
             self._emit(self.fwd, "stp_class_confusion", rows.buf.data_ptr(), target.buf.data_ptr(), rows.rows, classes, rows.C, self.cdt,
                        self.class_counts.data_ptr(), ws.data_ptr(), nb)
@@ -1443,10 +1451,35 @@ class Plan(object):
 
     def softmax_loss(self, logits, target, w_cce, w_dice, w_iou=0.0, w_jaccard=0.0, w_focal=0.0):
         """channel softmax + w_cce*categorical_crossentropy + w_dice*dice_loss [+ w*iou_loss + w*jaccard_loss + w*focal_loss on the
-        one-hot target: stp_softmax_loss_ex] (target = class index per pixel)."""
+        one-hot target: stp_softmax_loss_ex] (target = class index per pixel).  ``Plan.masked_loss`` = {"ignore_label": 0..255 or None,
+        "class_weights": one positive float per class or None} (set before define, as loss_scale is; the parameter list above is
+        pinned by tests/test_softmax_losses_host.py): stp_softmax_loss_masked (include/stp_hip.h has the arithmetic); None: the plan
+        of before."""
         if logits.C < 2:
             raise StpShapeError("categorical loss expects at least two classes")
         if self.dry:
+            return
+        opts = self.masked_loss or {}
+        ignore_label, class_weights = opts.get("ignore_label"), opts.get("class_weights")
+        if ignore_label is not None or class_weights is not None:
+            # one launch on the full-resolution logits, as under an extended spec: no low-resolution (_up) form, FPN / PSPNet keep
+            # their stp_resize_bilinear and its gradient launch.  The weights live in a plan-owned device tensor filled here.
+            if logits.C > 32:
+                raise StpShapeError("ignore_label / class_weights need a head of 2..32 classes")
+            ign = -1 if ignore_label is None else int(ignore_label)
+            cw = None
+            if class_weights is not None:
+                if len(class_weights) != logits.C:
+                    raise StpShapeError("class_weights: %d weights for %d classes" % (len(class_weights), logits.C))
+                cw = self._alloc((logits.C,), torch.float32)
+                cw.copy_(torch.tensor([float(w) for w in class_weights], dtype=torch.float32))
+            self.class_weights = cw
+            self.loss_scalars = self._alloc((16,), torch.float32)
+            self.loss_scalars.zero_()
+            self._emit_loss("stp_softmax_loss_masked", logits, target, (logits.rows, logits.C, logits.C),
+                            (w_cce, w_dice, w_iou, w_jaccard, w_focal), tail=(ign, cw.data_ptr() if cw is not None else None))
+            self._emit_confusion(logits, target, ignore_label=ign)
+            logits.grad_ready = self.training
             return
         if w_iou or w_jaccard or w_focal:
             # one launch on the full-resolution logits: the extended loss has no low-resolution (_up) form, so FPN / PSPNet keep
@@ -1562,7 +1595,7 @@ class Plan(object):
 
     # loss launches whose third argument is the element / pixel count of the batch ([N, ...] -> the first n_valid samples)
     LOSS_LAUNCHES = ("stp_sigmoid_bce_dice", "stp_softmax_cce_dice", "stp_prob_bce_dice", "stp_sigmoid_loss_ex", "stp_prob_cce_dice",
-                     "stp_sigmoid_multilabel_loss", "stp_softmax_loss_ex")
+                     "stp_sigmoid_multilabel_loss", "stp_softmax_loss_ex", "stp_softmax_loss_masked")
 
     def rerun_loss(self, n_valid):
         """Re-evaluates the loss / metric reduction over the first ``n_valid`` samples only (an evaluation batch whose tail
@@ -1570,7 +1603,7 @@ class Plan(object):
         as it is).  Samples are the slowest dimension of every tensor, so the real ones are a prefix of the element range.
         ``stp_lovasz_hinge`` ADDS its term to the scalars the first launch wrote, so it is re-run after it with
         ``images = n_valid`` (its third argument).  The confusion launch behind the loss (``class_metrics``) is re-run the same way
-        (``rerun_confusion``): its third argument is the pixel count (``stp_class_confusion``) or the image count (``_up``), and every
+        (``rerun_confusion``): its third argument is the pixel count (``stp_class_confusion``, ``_ignore``) or the image count (``_up``), and every
         call overwrites the counts."""
         n_valid = int(n_valid)
         if not 0 < n_valid <= self.N:
@@ -1599,7 +1632,7 @@ class Plan(object):
             raise ValueError("n_valid out of range")
         st = torch.cuda.current_stream().cuda_stream
         for fn, args, name, _meta in self.fwd:
-            if name in ("stp_class_confusion", "stp_class_confusion_up"):
+            if name in ("stp_class_confusion", "stp_class_confusion_up", "stp_class_confusion_ignore"):
                 a = list(args)
                 a[2] = n_valid if name.endswith("_up") else args[2] // self.N * n_valid      # images / pixels
                 _lib.check(fn(*a, st), name)

@@ -362,7 +362,8 @@ class TransformAugmentor(object):
         spec = cfg._aug_spec() if self.train else augment.resolve_paths(
             cfg.transforms, os.path.dirname(os.path.abspath(cfg.path)) if cfg.path else None)
         self.feeder = DeviceFeeder(self.device, (self.H, self.W), spec, seed=cfg.random_state if seed is None else seed,
-                                   classes=cfg.classes, channels=self.ch, activation=cfg.all.get("activation"))
+                                   classes=cfg.classes, channels=self.ch, activation=cfg.all.get("activation"),
+                                   ignore_label=getattr(cfg, "ignore_label", None))
 
     def augment_batches(self, batches):
         for b in batches:
@@ -451,11 +452,13 @@ def pack_multilabel(y, classes):
     return out
 
 
-def prepare_item(it, classes, pin, channels=3, activation=None):
+def prepare_item(it, classes, pin, channels=3, activation=None, ignore_label=None):
     """PredictionItem -> HostItem: uint8 pixels [h,w,channels] (RGB, or the first ``channels`` <= 7 bands of an N-channel image:
     ``shape: [H, W, C]`` in the YAML, reference segmentation.py:135-155) and label uint8 [h,w] ({0,1} for the sigmoid head, class
     index for the softmax head - one-hot maps are arg-maxed -, class bits for a multi-label sigmoid head: ``activation="sigmoid"``
-    with ``classes > 1``, see pack_multilabel).  This is the CPU work per sample; everything else happens on the GPU."""
+    with ``classes > 1``, see pack_multilabel).  ``ignore_label`` (softmax head): that value of a label image is kept as it is - the
+    loss and confusion kernels leave such pixels out -, every other value is clamped to classes - 1 as before; a one-hot mask cannot
+    carry a void label and is refused.  This is the CPU work per sample; everything else happens on the GPU."""
     x = np.asarray(it.x)
     if x.ndim == 2:
         x = x[:, :, None]
@@ -474,7 +477,12 @@ def prepare_item(it, classes, pin, channels=3, activation=None):
     elif is_multilabel(classes, activation):
         y = pack_multilabel(y, classes)
     elif y.shape[2] == classes:            # one-hot maps (what a Keras softmax head is fed) -> class index
+        if ignore_label is not None:
+            raise ValueError("item %r has a one-hot H x W x %d mask, which cannot carry a void label: with ignore_label: %d give "
+                             "H x W x 1 label images (pixel value = class index, %d = ignored)" % (it.id, classes, ignore_label, ignore_label))
         y = y.argmax(axis=2).astype(np.uint8)
+    elif ignore_label is not None:         # label image with a void value, kept
+        y = np.where(y[:, :, 0] == ignore_label, ignore_label, np.minimum(y[:, :, 0], classes - 1)).astype(np.uint8)
     else:                                  # label image
         y = np.minimum(y[:, :, 0], classes - 1).astype(np.uint8)
     xt, yt = torch.from_numpy(x), torch.from_numpy(np.ascontiguousarray(y))
@@ -504,7 +512,7 @@ class HostPrefetcher(object):
     GPU trains on the current one - the replacement of the reference's imgaug worker processes + bounded queue
     (FAQ.md:15-22; ``AUGMENTER_QUEUE_LIMIT``), minus the augmentation itself, which runs on the device."""
 
-    def __init__(self, ds, indexes, batch, classes, pin, depth=2, sampler=None, channels=3, activation=None):
+    def __init__(self, ds, indexes, batch, classes, pin, depth=2, sampler=None, channels=3, activation=None, ignore_label=None):
         """``sampler(n, h, w) -> (batch passes, per-image passes)`` (augment.sample_batch_staged): when given and a batch's items
         share one size, the thread also packs the batch into two pinned blocks and samples its augmentation passes (HostBatch)."""
         import queue
@@ -528,7 +536,7 @@ class HostPrefetcher(object):
             try:
                 for s in range(0, len(indexes), batch):
                     self.q.put(pack([prepare_item(ds[int(i)], classes, False if sampler is not None else pin, channels,
-                                                  activation)
+                                                  activation, ignore_label)
                                      for i in indexes[s:s + batch]]))
             except BaseException as e:      # surfaced on the consumer side
                 self._err = e
@@ -552,9 +560,10 @@ class DeviceFeeder(object):
     stream (they overlap the previous step's kernels), then one ``stp_augment_u8`` launch per item on the compute stream
     that resizes to the network shape and augments when training (+ ``stp_filter_u8`` passes for neighbourhood filters)."""
 
-    def __init__(self, device, out_hw, spec, seed, classes=1, channels=3, activation=None):
+    def __init__(self, device, out_hw, spec, seed, classes=1, channels=3, activation=None, ignore_label=None):
         self.device, self.out_hw, self.spec, self.classes = torch.device(device), out_hw, spec, int(classes)
         self.activation = activation           # the head's activation: "sigmoid" with classes > 1 = multi-label masks
+        self.ignore_label = ignore_label       # softmax head: the label-image value prepare_item keeps (HipSegModel.ignore_label)
         self.channels = int(channels)          # image channels of the network input (3, or 4..7 for N-channel models)
         self.rng = np.random.RandomState(seed)
         self.pin = self.device.type == "cuda"
@@ -568,7 +577,7 @@ class DeviceFeeder(object):
         oh, ow = self.out_hw
         if isinstance(items, HostBatch) and items.X.shape[0] == n:
             return self._feed_block(plan, items)
-        items = [it if isinstance(it, HostItem) else prepare_item(it, self.classes, self.pin, self.channels, self.activation)
+        items = [it if isinstance(it, HostItem) else prepare_item(it, self.classes, self.pin, self.channels, self.activation, self.ignore_label)
                  for it in items]
         ch = self.channels
         main = torch.cuda.current_stream()
@@ -723,7 +732,7 @@ class Trainer(object):
         rng = np.random.RandomState(f.rng.randint(0, 2 ** 31 - 1))
         sampler = lambda n, h, w: augment.sample_batch_staged(f.spec if training else [], rng, n, h, w, oh_ow)
         return HostPrefetcher(self.ds, [int(i) for i in indexes], batch, f.classes, f.pin, sampler=sampler, channels=f.channels,
-                              activation=getattr(f, "activation", None))
+                              activation=getattr(f, "activation", None), ignore_label=getattr(f, "ignore_label", None))
 
     def run_epoch_sums(self, indexes, training):
         """One pass over ``indexes`` -> ({log name: sum over batches of value * real samples of the batch}, real samples).
@@ -879,6 +888,9 @@ class GenericTaskConfig(object):
         self.transforms = aug_list(a.get("transforms"))
         self.dtype = a.get("dtype", "bf16")          # "bf16" | "fp16" | "fp32" (a key of this backend)
         self.loss_scale = a.get("loss_scale")        # fp16 only: static loss scale (default 2^14)
+        # softmax heads (keys of this backend): the label-image value left out of loss, gradient and metrics; one weight per class
+        self.ignore_label = a.get("ignore_label")
+        self.class_weights = a.get("class_weights")
         self.gpus = int(a.get("gpus", 1))
         self.inference_batch = int(a.get("inference_batch", self.batch))
         self.showDataExamples = False
@@ -947,6 +959,10 @@ class GenericTaskConfig(object):
         device = "cuda:%d" % distributed.device_index(local_rank)
         # (the switch is passed only where it is on: a compile() without the keyword keeps working for every other experiment)
         extra = {"class_metrics": True} if self._wants_class_metrics(model, stage) else {}
+        if self.ignore_label is not None:
+            extra["ignore_label"] = self.ignore_label
+        if self.class_weights is not None:
+            extra["class_weights"] = list(self.class_weights) if isinstance(self.class_weights, (list, tuple)) else self.class_weights
         model.compile(optimizer=self.optimizer, loss=loss, lr=lr, batch=self.batch, dtype=self.dtype, clipnorm=self.clipnorm,
                       clipvalue=self.clipvalue, metrics=self.metrics, device=device, use_graph=use_graph,
                       loss_scale=float(self.loss_scale) if self.loss_scale else None, **extra)
@@ -1065,7 +1081,8 @@ class GenericTaskConfig(object):
                 impl.reducer.reset_bounds()
         H, W = impl.H, impl.W                                  # = shape, or shape / crops
         feeder = DeviceFeeder(impl.device, (H, W), self._aug_spec(), seed=self.random_state * 7919 + fold * 101 + si,
-                              classes=self.classes, channels=impl.in_ch, activation=getattr(impl, "head_activation", None))
+                              classes=self.classes, channels=impl.in_ch, activation=getattr(impl, "head_activation", None),
+                              ignore_label=getattr(impl, "ignore_label", None))
         cbs = stage.callbacks()
         trainer = Trainer(impl, feeder, ds, cbs, rank, world)
         train_idx = kf.sampledIndexes(fold, True, stage.negatives)
@@ -1157,7 +1174,7 @@ class GenericTaskConfig(object):
         impl = model.impl
         H, W = impl.H, impl.W                                  # = shape, or shape / crops: the size of the plan's input buffers
         feeder = DeviceFeeder(impl.device, (H, W), self._aug_spec(), seed=self.random_state, classes=self.classes, channels=impl.in_ch,
-                              activation=getattr(impl, "head_activation", None))
+                              activation=getattr(impl, "head_activation", None), ignore_label=getattr(impl, "ignore_label", None))
         trainer = Trainer(impl, feeder, d, [], 0, 1)
         nb = max(1, -(-len(idx) // impl.batch)) * int(epochs)
         finder = LRFinder(float(start_lr), float(end_lr), nb)
