@@ -504,7 +504,7 @@ class HipSegModel(object):
             return
         p = self.plan
         saved = [t.clone() for t in self._mutable_state()]
-        p.run_prep_fwd(); p.run(p.bwd); p.run(p.opt)
+        p.run(p.prep); p.run(p.fwd); p.run(p.bwd); p.run(p.opt)
         torch.cuda.synchronize()
         for t, s in zip(self._mutable_state(), saved):
             t.copy_(s)
@@ -514,7 +514,7 @@ class HipSegModel(object):
         if segs is None:
             gfb = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gfb, capture_error_mode=CAPTURE_MODE):
-                p.run_prep_fwd(); p.run(p.bwd)
+                p.run(p.prep); p.run(p.fwd); p.run(p.bwd)
             self._graphs = {"fb": gfb, "opt": gopt}
         else:
             # one graph per backward segment; the first also holds the weight copies, the forward and the loss
@@ -523,7 +523,7 @@ class HipSegModel(object):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
                     if i == 0:
-                        p.run_prep_fwd()
+                        p.run(p.prep); p.run(p.fwd)
                     p.run(p.bwd[a:b])
                 gs.append(g)
                 a = b
@@ -566,7 +566,7 @@ class HipSegModel(object):
             if self.use_graph:
                 self._graphs["fb"].replay()
             else:
-                p.run_prep_fwd(); p.run(p.bwd)
+                p.run(p.prep); p.run(p.fwd); p.run(p.bwd)
             return
         self._works, a = [], 0
         for i, (b, ranges) in enumerate(segs):
@@ -574,7 +574,7 @@ class HipSegModel(object):
                 self._graphs["segs"][i].replay()
             else:
                 if i == 0:
-                    p.run_prep_fwd()
+                    p.run(p.prep); p.run(p.fwd)
                 p.run(p.bwd[a:b])
             a = b
             for s, e in ranges:

@@ -113,17 +113,7 @@ class Plan(object):
         self.bn_momentum = 0.99
         self.fuse_bn_backward = os.environ.get("STP_FUSE_BN_BACKWARD", "1") != "0"
         self.fuse_bn_backward_last = os.environ.get("STP_FUSE_BN_BACKWARD_LAST", "1") != "0"
-        # weight gradients (needed only by the optimizer / all-reduce) run on a second stream next to the data-gradient
-        # + BatchNormalization-backward chain of the same layer: the small latency-bound kernels of one chain fill the
-        # tails of the other's GEMMs (captured into the same hipGraph as a fork/join)
-        # Round 3: OFF by default.  With the row-of-taps layers grouped into a few long launches (stp_wgrad_group_*) the second
-        # stream no longer pays: same box, 40 graph steps, U-Net/ResNet34 bs16 - one stream 7.97 ms, two streams 8.07 ms (the grouped
-        # launch holds every CU's LDS, the main chain waits for it either way), per-layer launches on two streams 8.38 ms
-        # (profiles/r03c_ab.txt).  STP_SIDE_STREAM_WGRAD=1 restores the fork / join schedule.
-        self.side_stream_wgrad = os.environ.get("STP_SIDE_STREAM_WGRAD", "0") != "0"
         self.fold_upsample_grad = os.environ.get("STP_FOLD_UPSAMPLE_GRAD", "1") != "0"
-        self._side = None
-        self._side_reads = set()
         # grouped weight gradients (stp_wgrad_group_*): the row-of-taps layers of a stage are collected and issued as ONE partial
         # + ONE reduce launch once their work reaches this many GFLOP (0: every layer is launched alone, as in round 2)
         self.wgrad_group_gflop = float(os.environ.get("STP_WGRAD_GROUP_GFLOP", "300"))
@@ -136,15 +126,11 @@ class Plan(object):
         # step - FPN/ResNet50 14.62 -> 14.77 ms, PSPNet/ResNet101 8.06 -> 8.07, U-Net/ResNet34 6.350 -> 6.370 (same box, two interleaved
         # repetitions, profiles/r06e_step_ab.txt): the 59 / 30 / 7 launches saved (~9 us each in the eager table, ~3 in the graph) cost less
         # than reading 1 - 16 MB of slabs per layer back from HBM instead of from the cache the partial launch just wrote them through
-        self.reduce_batch = int(os.environ.get("STP_WGRAD_REDUCE_BATCH", "0")) if not self.side_stream_wgrad else 0
+        self.reduce_batch = int(os.environ.get("STP_WGRAD_REDUCE_BATCH", "0"))
         self._pending_reduces, self._pending_reduce_hi = [], 0
         self._wgroup, self._wgroup_cls, self._wgroup_flops, self._wgroup_hi = [], 0, 0.0, 0
         self._wgroup_reads = set()      # dY buffers of the pending layers: nothing may rewrite them before the group is issued
         self.wgroups = []               # (layer names, class) of every issued group (inspection / tests)
-        # STP_WGRAD_GROUP_JOIN=0: a grouped launch in flight is NOT joined at the next layer (only where a buffer it reads is
-        # rewritten, and at the end of the launch list); per-layer weight-gradient chains keep their lag-1 join
-        self._side_lag_join = os.environ.get("STP_WGRAD_GROUP_JOIN", "1") != "0"
-        self._side_groups_only = True   # nothing but grouped launches has been forked since the last join
         self._dw_ws_bytes = 0
         self.step_state = None
         # fused BatchNormalization sums in fixed-point slots (stp_conv_params.stats_slots): no finalize kernels
@@ -207,8 +193,7 @@ class Plan(object):
         self._upc4_layers = []
         self.tensors = OrderedDict()
         net_fn(self)
-        self._fuse_bn_into_consumers()
-        self._fuse_bn_finalize()
+        self._fuse_bn_finalize(self._fuse_bn_into_consumers())
         self._finish_prep()
         if self.training:
             # bwd_marks[i] = (launches issued after the i-th backward closure, lowest gradient offset written so far):
@@ -325,32 +310,18 @@ class Plan(object):
         return t
 
     def _gradbuf(self, t):
-        """Gradient buffer of ``t`` for a main-stream kernel that is about to WRITE it.  If a weight-gradient chain
-        still in flight on the side stream reads that buffer (a dY aliased as a residual gradient), join first."""
+        """Gradient buffer of ``t`` for a kernel that is about to WRITE it (a dY aliased as a residual gradient may still be
+        the operand of a pending grouped weight gradient: _guard_write)."""
         if t.grad is None:
             t.grad = self._alloc((t.N, t.H, t.W, t.gradC))
         self._guard_write(t.grad)
         return t.grad
 
     def _guard_write(self, buf):
-        """The hazard rule for a main-stream kernel about to write ``buf``."""
-        if self._wgroup_reads and buf.data_ptr() in self._wgroup_reads:
-            self._flush_wgroup()          # a pending grouped weight gradient reads this buffer as its dY: issue it first
-        if self._side_reads and buf.data_ptr() in self._side_reads:
-            self._join_side()
-
-    def _join_side(self):
-        """The main stream waits for the weight-gradient side chain: nothing in flight reads anything afterwards."""
-        self._mark(self.bwd, "join")
-        self._side_reads.clear()
-        self._side_groups_only = True
-
-    def _before_inplace_write(self, buf):
-        """A main-stream kernel is about to rewrite ``buf`` in place (stp_relu_bwd masks a dY): a pending grouped weight gradient
-        that still reads it as its dY is issued first, a side chain in flight that reads it is joined (the rule _gradbuf applies
-        to gradient buffers it hands out; advisor finding, round 3: no current network aliases such a buffer, nothing guarded it)."""
-        if buf is not None:
-            self._guard_write(buf)
+        """The hazard rule for a kernel about to write ``buf`` (None: nothing to write) - a gradient buffer _gradbuf hands out, or a dY
+        that stp_relu_bwd masks in place: a pending grouped weight gradient that still reads it as its dY is issued first."""
+        if buf is not None and self._wgroup_reads and buf.data_ptr() in self._wgroup_reads:
+            self._flush_wgroup()
 
     @staticmethod
     def _use(*ts):
@@ -405,11 +376,11 @@ class Plan(object):
           while staging it): the stp_bn_apply launch is dropped; ``tensor(name)`` still materialises the tensor on demand;
         * some consumers are halo-kernel convolutions (conv_halo.hip: the forward normalises the slab in LDS): when every one of
           their weight gradients runs on the row-of-taps kernel (conv_wgrad.hip normalises its halo tile the same way) the launch
-          is dropped as well; otherwise a weight gradient still reads the normalised tensor, the stp_bn_apply launch stays and
-          moves to the SIDE stream - off the forward's critical chain conv -> finalize -> apply -> conv.
+          is dropped as well; otherwise a weight gradient still reads the normalised tensor and the stp_bn_apply launch stays, a
+          launch of its own (returned: the ids of these records, which _fuse_bn_finalize leaves alone).
 
         The data gradient and the BatchNormalization backward never read the normalised tensor."""
-        drop, side = set(), set()
+        drop, kept = set(), set()
         for t in self.tensors.values():
             rec, sc, halo = t.meta.get("apply_rec"), t.meta.get("sc_consumers") or [], t.meta.get("halo_consumers") or []
             if rec is None or not (sc or halo) or len(sc) + len(halo) != t.meta.get("uses", 0):
@@ -423,46 +394,27 @@ class Plan(object):
                 if not halo or halo_full:
                     self._set_src_bn(wp, bn)
             if halo and not halo_full:
-                side.add(id(rec))
+                kept.add(id(rec))
             else:
                 t.meta["deferred"] = rec
                 t.meta["src_override"] = bn[0]
                 drop.add(id(rec))
-        if drop or side:
-            # every cross-stream edge of the step graph costs a queue hand-off: the deferred launches are issued in batches
-            # behind ONE fork (their only readers run in the backward pass, so any point of the forward is early enough)
-            batch = int(os.environ.get("STP_BN_SIDE_BATCH", "8"))
-            out, pending = [], []
+        self.fwd = [r for r in self.fwd if id(r) not in drop]
+        return kept
 
-            def flush():
-                if pending:
-                    out.append((None, (), "fork", None))                      # the side stream waits for the statistics
-                    out.extend(pending)
-                    del pending[:]
-            for r in self.fwd:
-                if id(r) in drop:
-                    continue
-                if id(r) in side:
-                    pending.append((r[0], r[1], r[2], dict(r[3] or {}, stream=1)))
-                    if len(pending) >= batch:
-                        flush()
-                    continue
-                out.append(r)
-            flush()
-            self.fwd = out
-
-    def _fuse_bn_finalize(self):
+    def _fuse_bn_finalize(self, keep=()):
         """stp_bn_finalize directly followed by the stp_bn_apply of the same BatchNormalization -> ONE stp_bn_finalize_apply launch where
         the library takes it (16-bit dtype, whole 64-channel slabs, <= 128 partial-sum columns): the apply pass reduces the partial
         sums of its own channel slab in its prologue, the single-workgroup-per-channel finalize launch (~5 us of latency on the
-        critical chain conv -> finalize -> apply -> conv) disappears.  The backward pair is merged inside stp_bn_backward_fused(_add)."""
+        critical chain conv -> finalize -> apply -> conv) disappears.  The backward pair is merged inside stp_bn_backward_fused(_add).
+        ``keep``: ids of stp_bn_apply records that stay launches of their own (_fuse_bn_into_consumers)."""
         if os.environ.get("STP_BN_FUSE_FINALIZE", "1") == "0":
             return
         out, i, fwd = [], 0, self.fwd
         while i < len(fwd):
             r = fwd[i]
             nxt = fwd[i + 1] if i + 1 < len(fwd) else None
-            if (r[2] == "stp_bn_finalize" and nxt is not None and nxt[2] == "stp_bn_apply" and not (nxt[3] or {}).get("stream")
+            if (r[2] == "stp_bn_finalize" and nxt is not None and nxt[2] == "stp_bn_apply" and id(nxt) not in keep
                     and nxt[1][7] == r[1][6] and nxt[1][8] == r[1][7] and nxt[1][1] == nxt[1][3] == self.cdt and nxt[1][5] == nxt[1][6] == r[1][3]
                     and nxt[1][12] == 0.0):
                 part, tiles, rows, Cn, eps, mom, mean, rstd, mm, mv = r[1]
@@ -496,13 +448,6 @@ class Plan(object):
         buf = self._alloc((nbytes // 4,), torch.float32)
         return buf.data_ptr(), nbytes
 
-    def _emit_side(self, lst, fname, *args):
-        lst.append((getattr(self.lib, fname), args, fname, {"stream": 1}))
-
-    @staticmethod
-    def _mark(lst, what):
-        lst.append((None, (), what, None))
-
     def _group_stats(self, p, st, Cs):
         """Group-level pre-reduction of a convolution's statistic columns (stp_conv_params.stats_group): where the kernel that serves
         ``p`` has the epilogue and its table has more than 128 columns, the launch also writes a [2][Cs][columns / G] table that the
@@ -526,18 +471,15 @@ class Plan(object):
             meta = dict(meta, pw=(int(p.C0), int(p.Cout)))                  # the pointwise streaming kernel's instance <Cin, Cout, ...> (bench.py)
         lst.append((self.lib.stp_conv2d, (C.byref(p),), "stp_conv2d", meta))
 
-    def _emit_wgrad(self, p, name, flops, reads, defer_hi=0):
-        """The weight gradient of ONE layer, forked onto the side chain (``reads``: the dY buffers it reads): split partial sums +
-        fixed-order reduce, two launch records so that each kernel can be timed on its own (bench.py) - same arithmetic as stp_conv2d_wgrad.
+    def _emit_wgrad(self, p, name, flops, defer_hi=0):
+        """The weight gradient of ONE layer: split partial sums + fixed-order reduce, two launch records so that each kernel can be
+        timed on its own (bench.py) - same arithmetic as stp_conv2d_wgrad.
         ``defer_hi`` > 0 (the end of the layer's range in the gradient arena; only when nothing reads dW before the optimizer): a layer
         with plain slabs writes them into a workspace of its own and its reduce joins the pending table (_flush_reduces)."""
         lst = self.bwd
-        self._mark(lst, "fork")
-        self._side_groups_only = False
-        self._side_reads.update(reads)
         self._keep.append(p)
         meta = {"layer": name, "pass": "wgrad", "flops": flops, "cout": p.Cout, "sc": bool(self.lib.stp_wgrad_sc_eligible(C.byref(p))),
-                "kernel_id": int(self.lib.stp_conv2d_wgrad_kernel_id(C.byref(p))), "stream": 1}
+                "kernel_id": int(self.lib.stp_conv2d_wgrad_kernel_id(C.byref(p)))}
         if defer_hi > 0 and self.reduce_batch > 0:
             db = int(self.lib.stp_wgrad_reduce_desc_bytes())
             wsb = int(self.lib.stp_conv2d_wgrad_workspace_bytes(C.byref(p)))
@@ -554,8 +496,7 @@ class Plan(object):
             self._keep = [t for t in self._keep if t is not ws]          # (row-of-taps slabs: the layer keeps its own reduce launch)
         lst.append((self.lib.stp_conv2d_wgrad_partial, (C.byref(p), self.ws_wgrad.data_ptr(), self.ws_wgrad.numel() * 4, 0),
                     "stp_conv2d_wgrad", meta))
-        lst.append((self.lib.stp_conv2d_wgrad_reduce, (C.byref(p), self.ws_wgrad.data_ptr(), 0), "stp_conv2d_wgrad_reduce",
-                    {"stream": 1}))
+        lst.append((self.lib.stp_conv2d_wgrad_reduce, (C.byref(p), self.ws_wgrad.data_ptr(), 0), "stp_conv2d_wgrad_reduce", None))
 
     def _flush_reduces(self):
         """One stp_wgrad_reduce_batched launch for the pending lone-layer reduces (see _emit_wgrad)."""
@@ -564,16 +505,15 @@ class Plan(object):
         table = b"".join(d for d, _ in self._pending_reduces)
         dev = self._table(table)
         n, maxc = len(self._pending_reduces), max(c for _, c in self._pending_reduces)
-        self.bwd.append((self.lib.stp_wgrad_reduce_batched, (dev.data_ptr(), n, maxc), "stp_wgrad_reduce_batched", {"stream": 1, "layers": n}))
+        self.bwd.append((self.lib.stp_wgrad_reduce_batched, (dev.data_ptr(), n, maxc), "stp_wgrad_reduce_batched", {"layers": n}))
         self._pending_reduces, self._pending_reduce_hi = [], 0
 
     def _flush_wgroup(self):
         """Issues the pending grouped weight gradient: descriptor table (built now - every pointer is final), one partial launch
-        and one reduce launch on the side stream.  Each group owns its partial-slab workspace."""
+        and one reduce launch.  Each group owns its partial-slab workspace."""
         if not self._wgroup:
             return
         layers, cls = self._wgroup, self._wgroup_cls
-        reads = self._wgroup_reads
         self._wgroup, self._wgroup_cls, self._wgroup_flops, self._wgroup_hi, self._wgroup_reads = [], 0, 0.0, 0, set()
         n = len(layers)
         # (... unless the lone layer is large enough to fill the all-taps kernel by itself: FPN's 512 -> 512 3x3 `fpn_final` at 4 x 256 x 256,
@@ -583,7 +523,7 @@ class Plan(object):
             # a lone layer gains nothing from the work list (measured on the bottleneck ResNets, whose 3x3 layers never neighbour:
             # FPN/ResNet50 1024x1024 18.25 -> 17.85 ms, PSPNet/ResNet101 768x768 10.13 -> 10.03 ms with the per-layer launch and its
             # tuned split count); the 32-channel class exists only as a grouped kernel (the per-layer one pads it to 64)
-            self._emit_wgrad(*layers[0], reads)
+            self._emit_wgrad(*layers[0])
             return
         arr = (C.POINTER(_lib.WgradParams) * n)(*[C.pointer(wp) for wp, _, _ in layers])
         tb = int(self.lib.stp_wgrad_group_table_bytes(arr, n))
@@ -597,14 +537,11 @@ class Plan(object):
         self._keep += [arr, host] + [wp for wp, _, _ in layers]
         names = [nm for _, nm, _ in layers]
         self.wgroups.append((names, cls))
-        self._mark(self.bwd, "fork")
-        self._side_reads.update(reads)
         hdr = (C.c_int32 * 16).from_buffer_copy(bytes(host)[:64])      # WgGroupHeader: [14] = fused producer BN instance, [15] = all-taps tiles
         meta = {"layer": "group[%d]:%s..%s" % (n, names[0], names[-1]), "pass": "wgrad", "flops": sum(f for _, _, f in layers), "cout": cls,
-                "bm": cls, "layers": names, "stream": 1, "taps9": int(hdr[15]), "pbn": int(hdr[14])}
+                "bm": cls, "layers": names, "taps9": int(hdr[15]), "pbn": int(hdr[14])}
         self.bwd.append((self.lib.stp_wgrad_group_partial, (C.addressof(host), dev.data_ptr(), ws.data_ptr(), wsb), "stp_wgrad_group_partial", meta))
-        self.bwd.append((self.lib.stp_wgrad_group_reduce, (C.addressof(host), dev.data_ptr(), ws.data_ptr()), "stp_wgrad_group_reduce",
-                         {"stream": 1}))
+        self.bwd.append((self.lib.stp_wgrad_group_reduce, (C.addressof(host), dev.data_ptr(), ws.data_ptr()), "stp_wgrad_group_reduce", None))
 
     # ------------------------------------------------------------------ layers
     def input_u8(self, name, H, W, Cn):
@@ -922,7 +859,7 @@ class Plan(object):
             dy = out.grad
             if out.gradC != Cn:
                 raise StpShapeError("%s: standalone ReLU needs an unpadded channel count" % name)
-            self._before_inplace_write(dy)
+            self._guard_write(dy)
             self._emit(self.bwd, "stp_relu_bwd", out.buf.data_ptr(), dy.data_ptr(), x.rows * Cn, self.cdt)
             if not x.grad_ready and x.gradC == out.gradC:
                 x.grad, x.grad_ready = dy, True
@@ -1541,57 +1478,13 @@ class Plan(object):
     def run(self, launches):
         if self.device.type != "cuda":
             raise _lib.StpError("plans execute on the GPU only (no CPU fallback)")
-        main = torch.cuda.current_stream()
-        st = main.cuda_stream
-        side, forked = None, False
-        for fn, args, name, meta in launches:
-            if fn is None:                      # stream markers of the weight-gradient side chain
-                if name == "fork" and self.side_stream_wgrad:
-                    side = self._side_stream()
-                    side.wait_stream(main)      # everything issued so far (dY of this layer) is visible to the side chain
-                    forked = True
-                elif name == "join" and forked:
-                    main.wait_stream(side)
-                    forked = False
+        st = torch.cuda.current_stream().cuda_stream
+        for fn, args, name, _meta in launches:
+            if fn is None:                      # the forward's "fused:resize->loss" marker: a name for inspection, no launch
                 continue
-            s = st
-            if meta is not None and meta.get("stream") and self.side_stream_wgrad:
-                if not forked:                  # a launch list cut between fork and its side launches (graph segments)
-                    side = self._side_stream()
-                    side.wait_stream(main)
-                    forked = True
-                s = side.cuda_stream
-            rc = fn(*args, s)
+            rc = fn(*args, st)
             if rc != 0:
                 _lib.check(rc, name)
-        if forked:
-            main.wait_stream(side)
-
-    # launches that read neither the weight compute copies nor the slot arena: they may run next to the weight preparation
-    _PREP_FREE = ("stp_bn_stats", "stp_bn_apply", "stp_bn_inference", "stp_counter_tick")
-
-    def run_prep_fwd(self):
-        """``run(prep); run(fwd)`` with the weight compute copies (they depend on the master parameters only) on the side stream, next to
-        the input BatchNormalization of the raw image (statistics + normalisation: ~25 us of small launches against ~55 us of weight
-        copies on U-Net/ResNet34) - joined before the first launch that reads a weight.  Captured into the step's hipGraph as a
-        fork / join.  OPT-IN (STP_PREP_SIDE=1): measured SLOWER - 7.27 vs 7.13 ms per step on one box (profiles/r04j_schedule_ab.txt): a
-        fork / join inside a hipGraph costs far more (~0.14 ms here) than the 55 us of copies it hides."""
-        k = 0
-        while k < len(self.fwd) and self.fwd[k][2] in self._PREP_FREE:
-            k += 1
-        if os.environ.get("STP_PREP_SIDE", "0") != "1" or not self.prep or k == 0 or self.device.type != "cuda":
-            self.run(self.prep)
-            self.run(self.fwd)
-            return
-        main, side = torch.cuda.current_stream(), self._side_stream()
-        side.wait_stream(main)
-        for fn, args, name, _meta in self.prep:
-            rc = fn(*args, side.cuda_stream)
-            if rc != 0:
-                _lib.check(rc, name)
-        self.run(self.fwd[:k])
-        main.wait_stream(side)
-        self.run(self.fwd[k:])
 
     # loss launches whose third argument is the element / pixel count of the batch ([N, ...] -> the first n_valid samples)
     LOSS_LAUNCHES = ("stp_sigmoid_bce_dice", "stp_softmax_cce_dice", "stp_prob_bce_dice", "stp_sigmoid_loss_ex", "stp_prob_cce_dice",
@@ -1637,11 +1530,6 @@ class Plan(object):
                 a[2] = n_valid if name.endswith("_up") else args[2] // self.N * n_valid      # images / pixels
                 _lib.check(fn(*a, st), name)
 
-    def _side_stream(self):
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        return self._side
-
     def init_states(self):
         for name, (off, numel, init) in self.states.items():
             self.S[off:off + numel] = init
@@ -1666,7 +1554,7 @@ class Dgrad(object):
 # The plan of ONE convolution - one Plan.conv call, which documents the arguments: the layer's geometry and operands as attributes, one
 # method per planning step.  The constructor and `declare` run in both passes of Plan.define, `forward` in the real pass, `backward` from
 # the tape, in backward order.  Order is behaviour here: _gptr calls feed bwd_marks, _gradbuf calls may issue the pending weight-gradient
-# group or a join, so every call stays at its point of the launch list.
+# group, so every call stays at its point of the launch list.
 class ConvLayer(object):
 
     def __init__(self, plan, name, x, Cout, k, stride, pad, src1, upsample, residual, transpose, relu, same_tf, fold_shortcut, param_cols):
@@ -1817,19 +1705,14 @@ class ConvLayer(object):
 
     # ------------------------------------------------------------------ backward
     def backward(self):
-        """Backward entry (ReLU mask, lag-1 join, residual gradient), then the weight, bias and data gradients."""
+        """Backward entry (ReLU mask, residual gradient), then the weight, bias and data gradients."""
         pl, out, residual, b = self.plan, self.out, self.residual, self.b
         if not out.needs_grad or not out.grad_ready:
             return
         dy = self.dy = out.grad
         if self.relu:
-            pl._before_inplace_write(dy)
+            pl._guard_write(dy)
             pl._emit(pl.bwd, "stp_relu_bwd", out.buf.data_ptr(), dy.data_ptr(), out.rows * out.gradC, pl.cdt)
-        # lag-1 join: the previous convolution's weight-gradient chain finishes before this layer's kernels start.
-        # (Letting the side chain fall further behind - joining only on a buffer hazard, see _gradbuf - measured
-        # SLOWER, 11.15 vs 10.88 ms/step: the chain then reads dY / x long after the main chain left them in L2.)
-        if pl._side_lag_join or not pl._side_groups_only:
-            pl._join_side()
         # residual branch: d(residual) = dY
         if residual is not None and residual.needs_grad:
             if not residual.grad_ready and residual.gradC == out.gradC:
@@ -1851,8 +1734,8 @@ class ConvLayer(object):
             # (folded: a projection shortcut whose data gradient rode in its sibling's launch - fold_shortcut: nothing to issue)
             self._data_grad()
 
-    # weight gradient: on the side stream, forked here (dY is final); joined before any kernel rewrites dY (_gradbuf)
-    # and at the end of the launch list
+    # weight gradient: issued here (dY is final), or collected into the pending group, which is issued before any kernel
+    # rewrites a dY it reads (_guard_write) and at the end of the launch list at the latest
     def _weight_grad(self):
         """Destination (the arena, or a padded / column-range matrix), the launch - grouped or alone - and the copy back from such a matrix."""
         pl, x, src1, w, wp, k, Cout, Cin_master, param_cols = self.plan, self.x, self.src1, self.w, self.wp, self.k, self.Cout, self.Cin_master, self.param_cols
@@ -1873,18 +1756,18 @@ class ConvLayer(object):
             # a layer outside the groups (stride 2, 1x1, stem, small-channel): the pending group is issued first, so a group
             # = consecutive row-of-taps layers (a network stage) and the gradient arena stays final above the last visited layer
             pl._flush_wgroup()
-            # (reads: see _gradbuf - dY is the only buffer of the chain that is ever rewritten; a padded dW is unpadded right below)
-            pl._emit_wgrad(wp, self.name, self.flops, {self.dy.data_ptr()}, defer_hi=0 if (padded or gcols is not None) else w.end)
+            # (a padded dW is unpadded right below)
+            pl._emit_wgrad(wp, self.name, self.flops, defer_hi=0 if (padded or gcols is not None) else w.end)
         if gcols is not None:
             # (the arena range of the shared kernel is reported final - _gptr, bwd_marks - by the last of its ranges only)
             w.pending_slices -= 1
             gbase = pl._gptr(w) if w.pending_slices == 0 else pl.G.data_ptr() + 4 * w.offset
-            pl._emit_side(pl.bwd, "stp_copy_cols_f32", gbase + 4 * int(param_cols[0]), int(param_cols[1]), gcols.data_ptr(), Cin_master, Cout, Cin_master, 0)
+            pl._emit(pl.bwd, "stp_copy_cols_f32", gbase + 4 * int(param_cols[0]), int(param_cols[1]), gcols.data_ptr(), Cin_master, Cout, Cin_master, 0)
         if padded:
-            pl._emit_side(pl.bwd, "stp_weight_grad_unpad", dwp.data_ptr(), pl._gptr(w), Cout, k, k, Cin_master, self.KWp, self.Cinp, 0)
+            pl._emit(pl.bwd, "stp_weight_grad_unpad", dwp.data_ptr(), pl._gptr(w), Cout, k, k, Cin_master, self.KWp, self.Cinp, 0)
         beta = x.meta.get("input_bn_beta")
         if self.stem and beta is not None and beta.trainable:
-            pl._emit_side(pl.bwd, "stp_stem_beta_grad", dwp.data_ptr(), pl._pptr(w), pl._gptr(beta), Cout, k, k, self.real_c0, self.KWp, self.Cinp, self.real_c0)
+            pl._emit(pl.bwd, "stp_stem_beta_grad", dwp.data_ptr(), pl._pptr(w), pl._gptr(beta), Cout, k, k, self.real_c0, self.KWp, self.Cinp, self.real_c0)
 
     # row-of-taps layer: joins the pending group (one launch per stage instead of one per layer); dY stays untouched
     # until the group is issued (_gradbuf / the BatchNormalization backward's out-of-place accumulate see to that)

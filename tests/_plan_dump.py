@@ -14,7 +14,7 @@ with ``diff``.  Plans build on ``device="cpu"``: nothing here needs a GPU.
 * An integer of 2^40 or more that resolves to no buffer is an error, not a token.
 
 ``python tests/_plan_dump.py OUT_DIR [plan ...]`` writes ``<plan>@<switch>.txt`` for every cell of PLANS x SWITCHES (or of the named plans)
-and prints one ``cell  records  sha256[:16]`` line each - the table of DESIGN.md 4.1 ("Plan.conv in steps").  To compare two versions of
+and prints one ``cell  records  sha256[:16]`` line each (22 plans x 19 switches = 418 cells; DESIGN.md 4.1 and 4.3 compare such tables).  To compare two versions of
 the plan builder, run it in a checkout of each and ``diff -r`` the two directories."""
 import bisect
 import ctypes as C
@@ -225,7 +225,7 @@ SWITCHES = [None, ("STP_HALO", "0"), ("STP_S2D", "0"), ("STP_SCATTER_1X1S2", "0"
             ("STP_HALO_FOLD_UP", "0"), ("STP_FUSE_UP_BN", "0"), ("STP_FOLD_UPSAMPLE_GRAD", "0"), ("STP_FUSE_BN_BACKWARD", "0"),
             ("STP_FUSE_BN_BACKWARD_LAST", "0"), ("STP_FUSE_BN_SC", "0"), ("STP_FUSE_BN_HALO", "1"), ("STP_BN_SLOTS", "1"),
             ("STP_BN_FUSE_FINALIZE", "0"), ("STP_WGRAD_GROUP_GFLOP", "0"), ("STP_WGRAD_LONE_GROUP_GFLOP", "0"), ("STP_WGRAD_REDUCE_BATCH", "4"),
-            ("STP_SIDE_STREAM_WGRAD", "1"), ("STP_WGRAD_GROUP_JOIN", "0"), ("STP_FUSE_POOL_BN", "1")]
+            ("STP_FUSE_POOL_BN", "1")]
 
 
 def cell_name(plan, switch):

@@ -450,8 +450,11 @@ def test_plan_structure_matches_unet_resnet34():
     assert bnames.count("stp_bn_backward_fused") + bnames.count("stp_bn_backward_fused_add") == 43 and bnames.count("stp_maxpool3x3s2_bwd_bn") == 0
     assert bnames.count("stp_bn_backward_fused_add") == 2              # stage1_unit3 / unit2 bn1 (the 16-pixel maps of stage 1 are grouped)
     assert bnames.count("stp_upsample2x_bwd_bn") == 3 and bnames.count("stp_upsample2x_bwd") == 0    # 5 decoder stages, two folded
-    # stream markers (honoured only with STP_SIDE_STREAM_WGRAD=1): one fork per per-layer chain and per group, a join at every convolution
-    assert bnames.count("fork") == 48 - grouped + 3 and bnames.count("join") == 48
+    # one stream: no list holds a fork / join marker, every backward record is a launch, no meta asks for a stream
+    records = plan.prep + plan.fwd + plan.bwd
+    assert not any(n in ("fork", "join") for _, _, n, _ in records)
+    assert all(callable(fn) for fn, _, _, _ in plan.bwd)
+    assert not any("stream" in m for _, _, _, m in records if m)
     assert "stp_add_inplace" not in bnames                             # every residual gradient aliases
     fl = sum(m["flops"] for _, _, _, m in plan.fwd if m)
     assert abs(fl / 2 / (2 * 1e6) - 31323 * (64 * 64) / (512 * 512)) < 2.0   # 31.3 GMAC/img at 512^2
@@ -460,6 +463,40 @@ def test_plan_structure_matches_unet_resnet34():
     frozen.define(lambda p: nets.unet_resnet(p, "resnet18", 64, 64))
     fb = [m["layer"] for _, _, n, m in frozen.bwd if n == "stp_conv2d_wgrad"] + [l for names_, _ in frozen.wgroups for l in names_]
     assert fb and all(l.startswith("decoder_") or l.startswith("final_") for l in fb)
+
+
+def test_resize_loss_marker_is_the_only_record_without_a_launch():
+    """PSPNet/ResNet50 192x192 batch 2, 20 classes: the head's resize is fused into the loss launch and leaves the one record of
+    the forward list that has no function - the marker ``fused:resize->loss``, which ``Plan.run`` skips."""
+    plan = graph.Plan(2, "bf16", "cpu", training=True)
+    plan.define(lambda p: nets.pspnet_resnet(p, "resnet50", 192, 192, classes=20))
+    assert [n for fn, _, n, _ in plan.fwd if fn is None] == ["fused:resize->loss"]
+    assert all(callable(fn) for fn, _, _, _ in plan.prep + plan.bwd)
+
+
+def test_backward_marks_count_launches():
+    """``Plan.bwd_marks`` on U-Net/ResNet34 64x64 batch 2: the end of each mark is the index just past the last launch its backward
+    closure issued (every record of ``bwd`` is a launch, so ``distributed.two_phase_bounds`` cuts at a share of the LAUNCHES), and the
+    last mark ends the list."""
+    ends = []
+
+    def net(p):
+        nets.unet_resnet(p, "resnet34", 64, 64)
+        if not p.dry:
+            def recorded(back):
+                def run():
+                    back()
+                    ends.append(len(p.bwd))
+                return run
+            p._tape = [recorded(back) for back in p._tape]
+    plan = graph.Plan(2, "bf16", "cpu", training=True)
+    plan.define(net)
+    assert all(callable(fn) for fn, _, _, _ in plan.bwd)
+    assert plan.bwd_marks[-1][0] == len(plan.bwd)
+    got = [e for e, _ in plan.bwd_marks]
+    assert len(ends) > 48 and got[:len(ends)] == ends                  # one mark per closure, at the end of its launches ...
+    assert got[len(ends):] in ([], [len(plan.bwd)])                    # ... and one more where a pending group is issued behind the last
+    assert got == sorted(got)
 
 
 def test_weight_gradient_groups_of_the_headline_workload():
