@@ -856,6 +856,49 @@ int stp_predict_accumulate(const float* probs, float* acc, int32_t N, int32_t H,
 int stp_predict_finish(const float* acc, int32_t H, int32_t W, int32_t C, int32_t k, int32_t mode, void* out, int32_t h, int32_t w,
                        int32_t out_ld, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Masks on the device (csrc/mask.hip): what is done with ONE image's finished fp32 map [h][w][C] (stp_predict_finish mode 0) - threshold,
+ * disk erosion / dilation, the run-length code, the counters of a threshold sweep.  uint8, fp32 and integers only (both builds export the
+ * same code); all of it exact integer work, equal to the host statement (numpy, scipy.ndimage, segmentation_pipeline/impl/rle.py) bit for
+ * bit.  No float atomics; element indices are int64; no result depends on an order.  Masks are uint8 {0, 1} (any non-zero input byte
+ * counts as 1).  STP_E_BADARG before any launch: a NULL pointer, a size <= 0, and what each entry lists.
+ *
+ *   stp_mask_threshold : out[y][x] (rows out_ld >= w bytes apart) = mode 0: map[y][x][channel] > threshold, compared in fp32 (the caller
+ *                        rounds its threshold to fp32 once - what `arr > 0.25` does on a float32 array; a NaN is never larger);  mode 1: the
+ *                        first index of the largest of the C values == channel (stp_predict_finish mode 2's rule; C <= 32; `threshold`
+ *                        unused).  One 16-byte store per 16 pixels where `out` is 16-byte aligned and out_ld % 16 == 0, else one byte per
+ *                        thread.  BADARG: channel outside 0..C-1, mode outside 0..1, out_ld < w, mode 1 with C > 32.
+ *   stp_mask_morph     : dst[h][w] = binary erosion (op 0) or dilation (op 1) of src[h][w] by the disk dx*dx + dy*dy <= r*r (skimage's
+ *                        disk(r)), 1 <= r <= 7, pixels outside the image reading as 0 for BOTH ops; src != dst.  Opening = erode, dilate;
+ *                        closing = dilate, erode: the pair equals scipy.ndimage.binary_opening / binary_closing(mask, disk(r)) with scipy's
+ *                        DEFAULTS (border_value = 0) - including that such a closing clears a band of r pixels at the image border (an
+ *                        all-ones 9 x 11 image closes to 35 ones with r = 2, and opens to 87).  LDS tiles of 64 rows x 256 columns of bits
+ *                        with an r-wide halo.  BADARG: r outside 1..7, op outside 0..1, src == dst.
+ *   stp_mask_rle       : the reference's run-length code of img[h][w]: pixels numbered 1-based COLUMN-major (x * h + y + 1); a run that
+ *                        reaches the bottom of a column and goes on at the top of the next is one run (the flat array decides).
+ *                        *count = number of runs, runs[k] = (start, length) int32 pairs for k < count, ascending; pairs past count are
+ *                        not written.  h * w < 2^31; capacity (pairs `runs` holds) >= (h*w + 1) / 2, the most an image can have, else
+ *                        BADARG; workspace (8-byte aligned) >= stp_mask_rle_workspace_bytes(h, w) (0 for sizes it refuses), else
+ *                        STP_E_WORKSPACE.  64 x 64 tiles are transposed through LDS into a column-major bit stream (global loads stay
+ *                        row-contiguous); run ends and the last run start are counted per workgroup, one workgroup scans them in order,
+ *                        a compacting launch writes the pairs.
+ *   stp_threshold_counts : ONE pass over the map for T <= 64 thresholds (a HOST pointer; finite and strictly ascending, else BADARG),
+ *                        against target[h][w] (uint8, non-zero = positive):  counts[t][0] = pixels with map[..][channel] > thresholds[t]
+ *                        (fp32 compare, a NaN never),  counts[t][1] = those of them with target != 0;  totals[0] = positives of the
+ *                        target, totals[1] = h * w.  int64 device outputs.  Per pixel j = #thresholds below the value goes into a
+ *                        workgroup's integer LDS table [T + 1][2]; a finalize launch sums the tables and takes the suffix sums.
+ *                        h * w < 2^40; workspace >= stp_threshold_counts_workspace_bytes(T) (0 for T outside 1..64), else
+ *                        STP_E_WORKSPACE. */
+int stp_mask_threshold(const float* map, int32_t h, int32_t w, int32_t C, int32_t channel, int32_t mode, float threshold, uint8_t* out,
+                       int32_t out_ld, void* stream);
+int stp_mask_morph(const uint8_t* src, uint8_t* dst, int32_t h, int32_t w, int32_t r, int32_t op, void* stream);
+size_t stp_mask_rle_workspace_bytes(int32_t h, int32_t w);
+int stp_mask_rle(const uint8_t* img, int32_t h, int32_t w, int32_t* runs, int32_t* count, int64_t capacity, void* workspace,
+                 size_t workspace_bytes, void* stream);
+size_t stp_threshold_counts_workspace_bytes(int32_t T);
+int stp_threshold_counts(const float* map, const uint8_t* target, int32_t h, int32_t w, int32_t C, int32_t channel, const float* thresholds,
+                         int32_t T, int64_t* counts, int64_t* totals, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

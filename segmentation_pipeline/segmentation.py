@@ -250,14 +250,13 @@ class PipelineConfig(generic.GenericTaskConfig):
         shape = (h, w) if mode == PipelineConfig.LABELS else (h, w, acc.shape[-1])
         return torch.empty(shape, dtype=torch.float32 if mode == PipelineConfig.PROBS else torch.uint8, device=acc.device)
 
-    def _predict_maps(self, models, ttflips, items, mode=0, original_size=True):
-        """The finished maps (numpy, ``mode``: PROBS / BYTES / LABELS) of up to one batch of items, at each item's own size (or, with
-        ``original_size=False`` and no ``crops``, at the network shape).  Resize, flips, the sum over models and flips, the mean, the
-        way back to the image's size and the quantisation all run on the device; the finished maps of a batch come back in one copy
-        when they share a size, one copy per item otherwise."""
+    def _predict_maps_device(self, models, ttflips, items, mode=0, original_size=True):
+        """``_predict_maps`` without the copy back: ``(maps, whole)`` - one DEVICE tensor per item (``mode``: PROBS / BYTES / LABELS, at
+        the item's own size or, ``original_size=False`` and no ``crops``, at the network shape), and, where the items share a size, the
+        one tensor [n * h, w, ...] whose row blocks they are (else None).  The mask methods go on from here on the device."""
         from segmentation_training_pipeline_amd import ops
         if self.crops:
-            return [self._predict_cells(models, ttflips, it.x, mode) for it in items]
+            return [self._predict_cells_device(models, ttflips, it.x, mode) for it in items], None
         impl0 = _impl(models[0])
         H, W = impl0.H, impl0.W
         acc, k = self.predict_on_batch_device(models, ttflips, self._resize_to_net(impl0, [it.x for it in items], device=True), len(items))
@@ -267,15 +266,27 @@ class PipelineConfig(generic.GenericTaskConfig):
             out = self._new_map(acc, mode, len(items) * h, w)
             for i in range(len(items)):
                 ops.predict_finish(acc[i], H, W, acc.shape[-1], k, mode, out[i * h:(i + 1) * h], h, w)
-            return list(out.cpu().numpy().reshape((len(items), h) + tuple(out.shape[1:])))
+            return [out[i * h:(i + 1) * h] for i in range(len(items))], out
         maps = []
         for i, (h, w) in enumerate(sizes):
             out = self._new_map(acc, mode, h, w)
             ops.predict_finish(acc[i], H, W, acc.shape[-1], k, mode, out, h, w)
-            maps.append(out.cpu().numpy())
-        return maps
+            maps.append(out)
+        return maps, None
 
-    def _predict_batches(self, spath, fold, stage, limit, ttflips, mode=0, original_size=True):
+    def _predict_maps(self, models, ttflips, items, mode=0, original_size=True):
+        """The finished maps (numpy, ``mode``: PROBS / BYTES / LABELS) of up to one batch of items, at each item's own size (or, with
+        ``original_size=False`` and no ``crops``, at the network shape).  Resize, flips, the sum over models and flips, the mean, the
+        way back to the image's size and the quantisation all run on the device; the finished maps of a batch come back in one copy
+        when they share a size, one copy per item otherwise."""
+        if self.crops:
+            return [self._predict_cells(models, ttflips, it.x, mode) for it in items]
+        maps, whole = self._predict_maps_device(models, ttflips, items, mode, original_size)
+        if whole is not None:
+            return list(whole.cpu().numpy().reshape((len(items), whole.shape[0] // len(items)) + tuple(whole.shape[1:])))
+        return [m.cpu().numpy() for m in maps]
+
+    def _predict_batches(self, spath, fold, stage, limit, ttflips, mode=0, original_size=True, device=False):
         from segmentation_pipeline.impl.datasets import DirectoryDataSet
         nets_ = self._models(fold, stage)
         ds = DirectoryDataSet(spath)
@@ -283,7 +294,10 @@ class PipelineConfig(generic.GenericTaskConfig):
         B = nets_[0].impl.batch
         for s in range(0, n, B):
             items = [ds[i] for i in range(s, min(s + B, n))]
-            yield items, self._predict_maps(nets_, ttflips, items, mode, original_size)
+            if device:
+                yield items, self._predict_maps_device(nets_, ttflips, items, mode, original_size)[0]
+            else:
+                yield items, self._predict_maps(nets_, ttflips, items, mode, original_size)
 
     def predict_on_directory(self, spath, fold=0, stage=0, limit=-1, batch_size=32, ttflips=False):
         """Yields (items, probabilities) per batch: a float32 array [n, H, W, classes] at the network shape, or - ``crops`` - the
@@ -295,6 +309,10 @@ class PipelineConfig(generic.GenericTaskConfig):
         """``crops: N`` at prediction time (README.md:488-491): the image is split into the N x N cells the model was trained
         on, every cell is predicted, scaled back to its own size and the map is assembled - invisible to the caller.  Each cell is
         finished into its rectangle of the full-size device map (stp_predict_finish with the map's row pitch); one copy brings it back."""
+        return self._predict_cells_device(models, ttflips, img, mode).cpu().numpy()
+
+    def _predict_cells_device(self, models, ttflips, img, mode=0):
+        """The assembled full-size map of ``_predict_cells``, left on the device."""
         from segmentation_training_pipeline_amd import ops
         from segmentation_training_pipeline_amd.pipeline import crop_bounds
         c = int(self.crops)
@@ -312,7 +330,7 @@ class PipelineConfig(generic.GenericTaskConfig):
                 r, q = divmod(s + j, c)
                 ops.predict_finish(acc[j], impl0.H, impl0.W, acc.shape[-1], k, mode, out[ys[r]:ys[r + 1], xs_[q]:xs_[q + 1]],
                                    cell.shape[0], cell.shape[1], out_ld=w)
-        return out.cpu().numpy()
+        return out
 
     def predict_to_directory(self, spath, tpath, fold=0, stage=0, limit=-1, batchSize=32, binaryArray=False, ttflips=False, labelMap=False):
         """Writes one prediction per image of ``spath`` into ``tpath``: ``<stem>.png`` = probability of channel 0 as bytes (a
@@ -364,6 +382,148 @@ class PipelineConfig(generic.GenericTaskConfig):
             yield EvalBatch(images=[it.x for it in items], data=[it.id for it in items],
                             segmentation_maps=[PredictedMap(np.asarray(it.y)) for it in items],
                             predicted_maps_aug=[PredictedMap(p) for p in maps])
+
+    # ---------------------------------------------------------------- masks on the device (csrc/mask.hip; README.md:498-525, :541-550)
+    SWEEP_METRICS = ("dice", "iou", "f2")
+
+    def _softmax_head(self):
+        return self.classes > 1 and self.all.get("activation") != "sigmoid"
+
+    def _mask_mode(self, threshold, opening, closing, channel):
+        """stp_mask_threshold's mode for this head (0: sigmoid map > threshold, 1: softmax argmax == channel), after the argument checks
+        every mask method makes before a model is loaded."""
+        if not 0 <= int(channel) < int(self.classes):
+            raise ValueError("channel %r: the head has %d class(es)" % (channel, self.classes))
+        for name, r in (("opening", opening), ("closing", closing)):
+            if int(r) != r or not 0 <= r <= 7:
+                raise ValueError("%s is the radius of a disk, 0 (off) to 7: got %r" % (name, r))
+        if self._softmax_head():
+            if threshold != 0.5:
+                raise ValueError("a softmax head has one label per pixel: the mask of `channel` is argmax == channel and takes no threshold")
+            return 1
+        return 0
+
+    def _device_mask(self, probs, mode, threshold, opening, closing, channel):
+        """One image's finished device map [h, w, classes] -> its uint8 {0, 1} device mask [h, w]: stp_mask_threshold, then the disk
+        opening (erode, dilate), then the disk closing (dilate, erode) - scipy.ndimage's binary_opening / binary_closing with defaults."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        h, w, C = (int(v) for v in probs.shape)
+        a = torch.empty((h, w), dtype=torch.uint8, device=probs.device)
+        ops.mask_threshold(probs, h, w, C, channel, mode, threshold, a)
+        if opening or closing:
+            b = torch.empty_like(a)
+            for r, first in ((opening, 0), (closing, 1)):
+                if r:
+                    ops.mask_morph(a, b, h, w, r, first)
+                    ops.mask_morph(b, a, h, w, r, 1 - first)
+        return a
+
+    @staticmethod
+    def _device_rle(mask):
+        """The reference's run-length string (impl.rle.rle_encode) of a device mask: stp_mask_rle, then the count and the first
+        ``count`` (start, length) pairs come back."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        h, w = (int(v) for v in mask.shape)
+        runs = torch.empty(((h * w + 1) // 2, 2), dtype=torch.int32, device=mask.device)
+        count = torch.empty(1, dtype=torch.int32, device=mask.device)
+        ws = torch.empty(ops.mask_rle_workspace_bytes(h, w), dtype=torch.uint8, device=mask.device)
+        ops.mask_rle(mask, h, w, runs, count, ws)
+        n = int(count.item())
+        return " ".join(map(str, runs[:n].reshape(-1).cpu().numpy().tolist()))      # "start length start length ..."
+
+    def predict_masks(self, spath, fold=0, stage=0, limit=-1, ttflips=False, threshold=0.5, opening=0, closing=0, channel=0, rle=True):
+        """README.md:498-525 without the host: a generator of ``(file_name, rle_string)`` - or, ``rle=False``, ``(file_name, uint8 h x w
+        mask)`` - per image of ``spath``.  Per image, on the device: the finished map at the image's own size (``fold`` may be a list,
+        ``ttflips`` and ``crops:`` as in ``predict_in_directory``), ``map[..., channel] > float32(threshold)`` (a softmax head: ``argmax
+        == channel``, no threshold), a disk(``opening``) opening, a disk(``closing``) closing (radius 0: off; both as
+        scipy.ndimage's binary_opening / binary_closing with defaults - that closing clears a band at the image border), the
+        run-length code.  Only the runs (or the mask) come back.  Connected-component clean-up (remove_small_objects,
+        remove_small_holes, multi_rle_encode) stays host code on the ``rle=False`` masks."""
+        mode = self._mask_mode(threshold, opening, closing, channel)      # (refusals fire here, not at the first next())
+
+        def masks():
+            for items, maps in self._predict_batches(spath, fold, stage, limit, ttflips, self.PROBS, device=True):
+                for it, probs in zip(items, maps):
+                    mask = self._device_mask(probs, mode, float(threshold), int(opening), int(closing), int(channel))
+                    yield it.id, (self._device_rle(mask) if rle else mask.cpu().numpy())
+        return masks()
+
+    def predict_to_csv(self, spath, csv_path, fold=0, stage=0, limit=-1, ttflips=False, threshold=0.5, opening=0, closing=0, channel=0,
+                       columns=("image", "rle_mask")):
+        """README.md:498-525 in one call: ``predict_masks`` written as a CSV with the header ``columns``; the image column holds the file
+        name up to its first ``.``.  Returns the number of rows."""
+        import csv
+        if len(columns) != 2:
+            raise ValueError("columns names the image column and the run-length column")
+        rows = self.predict_masks(spath, fold, stage, limit, ttflips, threshold, opening, closing, channel)
+        n = 0
+        with open(csv_path, "w", newline="") as f:
+            out = csv.writer(f, lineterminator="\n")
+            out.writerow(list(columns))
+            for name, code in rows:
+                out.writerow([name[0:name.index(".")] if "." in name else name, code])
+                n += 1
+        return n
+
+    @staticmethod
+    def sweep_score(metric, P, TP, G):
+        """float64 scores from integer counters (arrays broadcast): P predicted, TP true positive, G positives of the target.
+        dice 2TP / (P + G), iou TP / (P + G - TP), f2 5TP / (4G + P); 1 where P = G = 0."""
+        P, TP, G = (np.asarray(a, np.float64) for a in (P, TP, G))
+        num, den = {"dice": (2 * TP, P + G), "iou": (TP, P + G - TP), "f2": (5 * TP, 4 * G + P)}[metric]
+        empty = (P == 0) & (G == 0)
+        return np.where(empty, 1.0, num / np.where(empty, 1.0, den))
+
+    def find_threshold(self, ds, fold, stage=-1, negatives="real", ttflips=None, thresholds=None, metric="dice", average="image", channel=0):
+        """README.md:541-550 without the host passes: the threshold (of ``thresholds``, default d / 20 for d = 1..19) whose masks
+        ``map[..., channel] > threshold`` score best against the validation masks of ``fold`` (the items ``evaluateAll`` yields).  Each
+        image makes ONE stp_threshold_counts pass on the device; only the integer counters come back, and the scores are float64 on
+        the host: ``average="image"`` the mean of the per-image scores, ``"pixels"`` the score of the summed counters.  Returns
+        ``(best_threshold, {threshold: score})``; the first threshold wins a tie.  No opening inside the sweep."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        if self._softmax_head():
+            raise ValueError("find_threshold sweeps the threshold of a sigmoid map: a softmax head has none")
+        if metric not in self.SWEEP_METRICS:
+            raise ValueError("metric %r: one of %s" % (metric, ", ".join(self.SWEEP_METRICS)))
+        if average not in ("image", "pixels"):
+            raise ValueError("average %r: 'image' or 'pixels'" % (average,))
+        if not 0 <= int(channel) < int(self.classes):
+            raise ValueError("channel %r: the head has %d class(es)" % (channel, self.classes))
+        thresholds = [d / 20 for d in range(1, 20)] if thresholds is None else [float(t) for t in thresholds]
+        t32 = np.asarray(thresholds, np.float32)            # what the device compares with
+        if not 1 <= len(thresholds) <= 64:
+            raise ValueError("1 to 64 thresholds in one sweep: got %d" % len(thresholds))
+        if not np.isfinite(t32).all() or not (np.diff(t32) > 0).all():
+            raise ValueError("thresholds must be finite and strictly ascending (as float32)")
+        folds = self.kfold(ds, range(0, len(ds)))
+        indexes = [int(i) for i in folds.sampledIndexes(fold, False, negatives)]
+        if not indexes:
+            raise ValueError("fold %r has no validation items" % (fold,))
+        m = self.load_model(fold, stage)
+        dev, B, T = m.impl.device, m.impl.batch, len(thresholds)
+        counts = torch.empty((len(indexes), T, 2), dtype=torch.int64, device=dev)
+        totals = torch.empty((len(indexes), 2), dtype=torch.int64, device=dev)
+        ws = torch.empty(ops.threshold_counts_workspace_bytes(T), dtype=torch.uint8, device=dev)
+        for s in range(0, len(indexes), B):
+            items = [ds[i] for i in indexes[s:s + B]]
+            for j, (it, probs) in enumerate(zip(items, self._predict_maps_device([m], ttflips, items)[0])):
+                y = np.asarray(it.y)
+                plane = y if y.ndim == 2 else y[:, :, channel if y.shape[2] > 1 else 0]
+                h, w, C = (int(v) for v in probs.shape)
+                if plane.shape != (h, w):
+                    raise ValueError("item %r: a %s mask for a %d x %d image" % (it.id, plane.shape, h, w))
+                target = torch.from_numpy(np.ascontiguousarray(plane != 0).view(np.uint8)).to(dev)
+                ops.threshold_counts(probs, target, h, w, C, channel, t32, counts[s + j], totals[s + j], ws)
+        counts, totals = counts.cpu().numpy(), totals.cpu().numpy()          # the only copies back: 2 T + 2 integers per image
+        if average == "pixels":
+            scores = self.sweep_score(metric, counts[:, :, 0].sum(0), counts[:, :, 1].sum(0), totals[:, 0].sum())
+        else:
+            scores = self.sweep_score(metric, counts[:, :, 0], counts[:, :, 1], totals[:, :1]).mean(axis=0)
+        table = {t: float(v) for t, v in zip(thresholds, scores)}
+        return thresholds[int(np.argmax(scores))], table
 
 
 class PredictedMap(object):

@@ -214,6 +214,12 @@ SIGNATURES = {
     "stp_flip_u8": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "stp_predict_accumulate": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "stp_predict_finish": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp]),
+    "stp_mask_threshold": (i32, [vp, i32, i32, i32, i32, i32, f32, vp, i32, vp]),
+    "stp_mask_morph": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "stp_mask_rle_workspace_bytes": (sz, [i32, i32]),
+    "stp_mask_rle": (i32, [vp, i32, i32, vp, vp, i64, vp, sz, vp]),
+    "stp_threshold_counts_workspace_bytes": (sz, [i32]),
+    "stp_threshold_counts": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(f32), i32, vp, vp, vp, sz, vp]),
 }
 
 _libs = {}          # storage format ("bf16" | "fp16") -> loaded library

@@ -12,10 +12,10 @@
 // workspace, a finalize launch sums them: integer sums, so neither form depends on an order and graph replay is bit-identical.
 #include "loss_reduce.h"
 #include "softmax_row.h"
+#include "wave_count.h"      // wave_count(): the peel of up to WAVE_COUNT_PEEL (the CONF_PEEL of the comment above) keys
 
 #define CONF_THREADS 1024
 #define CONF_MAX_BLOCKS 512          // two workgroups per CU; stp_class_confusion_workspace_bytes() covers 512 tables
-#define CONF_PEEL 4
 
 template <int CM>
 __device__ __forceinline__ int first_argmax(const float (&p)[CM], int classes) {
@@ -28,21 +28,6 @@ __device__ __forceinline__ int first_argmax(const float (&p)[CM], int classes) {
     idx = up ? c : idx;
   }
   return idx;
-}
-
-// every lane of the wave calls this (key < 0: no pixel): table[key] += 1 for each lane with a pixel
-__device__ __forceinline__ void wave_count(int* table, int key) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long rem = __ballot(key >= 0);
-#pragma unroll 1
-  for (int r = 0; r < CONF_PEEL && rem; ++r) {
-    const int leader = __ffsll(rem) - 1;
-    const int k = __shfl(key, leader, 64);
-    const unsigned long long same = __ballot(key == k);      // (k >= 0: lanes without a pixel never match; the leader always does)
-    if (lane == leader) atomicAdd(table + k, __popcll(same));
-    rem &= ~same;
-  }
-  if ((rem >> lane) & 1ull) atomicAdd(table + key, 1);
 }
 
 // the workgroup's table (THREADS = its size): zeroed before the first pixel, written to its slot of the workspace after the last

@@ -380,3 +380,51 @@ def predict_finish(acc, H, W, Cn, k, mode, out, h, w, out_ld=None):
     if mode in (0, 1, 2) and out.dtype != (torch.float32 if mode == 0 else torch.uint8):
         raise ValueError("predict_finish: mode %d writes %s" % (mode, "float32" if mode == 0 else "uint8"))
     _lib.call("stp_predict_finish", ptr(_dev(acc)), H, W, Cn, int(k), int(mode), ptr(_dev(out)), h, w, out_ld, stream())
+
+
+# masks on the device (csrc/mask.hip): ONE image's finished fp32 map [h, w, Cn] -> uint8 {0, 1} masks, their run-length code, sweep counters
+def mask_threshold(probs, h, w, Cn, channel, mode, threshold, out, out_ld=None):
+    """``out`` uint8 [h, out_ld]: mode 0 ``probs[:, :, channel] > float32(threshold)``, mode 1 ``argmax == channel`` (first largest)."""
+    out_ld = w if out_ld is None else int(out_ld)
+    room = out.untyped_storage().nbytes() - out.storage_offset()
+    if probs.numel() < h * w * Cn or (out_ld >= w and room < (h - 1) * out_ld + w):
+        raise ValueError("mask_threshold: buffers are smaller than the maps")
+    if probs.dtype != torch.float32 or out.dtype != torch.uint8:
+        raise ValueError("mask_threshold: float32 in, uint8 out")
+    _lib.call("stp_mask_threshold", ptr(_dev(probs)), h, w, Cn, int(channel), int(mode), float(threshold), ptr(_dev(out)), out_ld, stream())
+
+
+def mask_morph(src, dst, h, w, r, op):
+    """``dst`` = erosion (op 0) / dilation (op 1) of the uint8 mask ``src`` [h, w] by disk(r), zeros outside the image."""
+    if min(src.numel(), dst.numel()) < h * w or src.dtype != torch.uint8 or dst.dtype != torch.uint8:
+        raise ValueError("mask_morph: two uint8 buffers of h x w")
+    _lib.call("stp_mask_morph", ptr(_dev(src)), ptr(_dev(dst)), h, w, int(r), int(op), stream())
+
+
+def mask_rle_workspace_bytes(h, w):
+    return int(_lib.load().stp_mask_rle_workspace_bytes(h, w))
+
+
+def mask_rle(img, h, w, runs, count, workspace):
+    """``runs`` int32 [capacity, 2] = (start, length) of the column-major runs of the uint8 mask ``img`` [h, w], ``count`` int32 [1]."""
+    if img.numel() < h * w or img.dtype != torch.uint8 or runs.dtype != torch.int32 or count.dtype != torch.int32 or count.numel() < 1:
+        raise ValueError("mask_rle: a uint8 image of h x w, int32 runs and count")
+    _lib.call("stp_mask_rle", ptr(_dev(img)), h, w, ptr(_dev(runs)), ptr(_dev(count)), runs.numel() // 2, ptr(_dev(workspace)),
+              workspace.numel() * workspace.element_size(), stream())
+
+
+def threshold_counts_workspace_bytes(T):
+    return int(_lib.load().stp_threshold_counts_workspace_bytes(T))
+
+
+def threshold_counts(probs, target, h, w, Cn, channel, thresholds, counts, totals, workspace):
+    """``counts`` int64 [T, 2] = (pixels above thresholds[t], those of them on the target), ``totals`` int64 [2] = (target positives, h * w);
+    ``thresholds``: a host sequence, rounded to float32 here."""
+    if probs.numel() < h * w * Cn or target.numel() < h * w or probs.dtype != torch.float32 or target.dtype != torch.uint8:
+        raise ValueError("threshold_counts: a float32 map of h x w x C and a uint8 target of h x w")
+    T = len(thresholds)
+    if counts.dtype != torch.int64 or totals.dtype != torch.int64 or counts.numel() < 2 * T or totals.numel() < 2:
+        raise ValueError("threshold_counts: int64 counts [T, 2] and totals [2]")
+    thr = (C.c_float * max(T, 1))(*[float(t) for t in thresholds])
+    _lib.call("stp_threshold_counts", ptr(_dev(probs)), ptr(_dev(target)), h, w, Cn, int(channel), thr, T, ptr(_dev(counts)), ptr(_dev(totals)),
+              ptr(_dev(workspace)), workspace.numel() * workspace.element_size(), stream())
