@@ -40,48 +40,25 @@ template <int THREADS> __device__ __forceinline__ void conf_table_store(const in
   for (int e = threadIdx.x; e < entries; e += THREADS) partial[(size_t)blockIdx.x * entries + e] = table[e];
 }
 
-template <typename T, int CM>
+// IGNORE (stp_class_confusion_ignore): a pixel whose stored target equals ignore_label keeps key -1 - its row is not loaded, it joins no
+// key group of the ballot peel and adds nothing, so the table's total is the number of counted pixels.  The other instance never
+// looks at the argument.
+template <typename T, int CM, bool IGNORE>
 __global__ __launch_bounds__(CONF_THREADS) void class_confusion_kernel(const T* __restrict__ rows, const uint8_t* __restrict__ target,
-                                                                       int64_t pixels, int classes, int ldc, int* __restrict__ partial) {
+                                                                       int64_t pixels, int classes, int ldc, int ignore_label,
+                                                                       int* __restrict__ partial) {
   __shared__ int table[STP_MAX_CLASSES * STP_MAX_CLASSES];
   conf_table_clear<CONF_THREADS>(table, classes * classes);
-  const bool vec = (ldc % Elem<T>::VEC) == 0 && CM % Elem<T>::VEC == 0;
-  const bool vec4 = !vec && sizeof(T) == 2 && (ldc % 4) == 0 && (CM % 4) == 0 && !(reinterpret_cast<uintptr_t>(rows) & 7);
-  // (the trip count is the same in every lane of a wave: wave_count is called by all 64)
-  for (int64_t base = (int64_t)blockIdx.x * CONF_THREADS; base < pixels; base += (int64_t)gridDim.x * CONF_THREADS) {
-    const int64_t i = base + threadIdx.x;
-    int key = -1;
-    if (i < pixels) {
-      float p[CM];
-      class_row_load<T, CM>(rows + i * ldc, classes, vec, p, vec4);
-      const int t = target[i] < classes ? target[i] : classes - 1;
-      key = t * classes + first_argmax<CM>(p, classes);
-    }
-    wave_count(table, key);
-  }
-  conf_table_store<CONF_THREADS>(table, classes * classes, partial);
-}
-
-// class_confusion_kernel with an ignore label (stp_class_confusion_ignore): a pixel whose stored target equals it keeps key -1 - it
-// joins no key group of the ballot peel and adds nothing, so the table's total is the number of counted pixels.  A kernel of its own:
-// the instances of class_confusion_kernel stay as they were compiled.
-template <typename T, int CM>
-__global__ __launch_bounds__(CONF_THREADS) void class_confusion_ignore_kernel(const T* __restrict__ rows, const uint8_t* __restrict__ target,
-                                                                              int64_t pixels, int classes, int ldc, int ignore_label,
-                                                                              int* __restrict__ partial) {
-  __shared__ int table[STP_MAX_CLASSES * STP_MAX_CLASSES];
-  conf_table_clear<CONF_THREADS>(table, classes * classes);
-  const bool vec = (ldc % Elem<T>::VEC) == 0 && CM % Elem<T>::VEC == 0;
-  const bool vec4 = !vec && sizeof(T) == 2 && (ldc % 4) == 0 && (CM % 4) == 0 && !(reinterpret_cast<uintptr_t>(rows) & 7);
+  const RowAccess ra = row_access<T, CM>(rows, ldc);
   // (the trip count is the same in every lane of a wave: wave_count is called by all 64)
   for (int64_t base = (int64_t)blockIdx.x * CONF_THREADS; base < pixels; base += (int64_t)gridDim.x * CONF_THREADS) {
     const int64_t i = base + threadIdx.x;
     int key = -1;
     if (i < pixels) {
       const int tr = target[i];
-      if (tr != ignore_label) {
+      if (!IGNORE || tr != ignore_label) {
         float p[CM];
-        class_row_load<T, CM>(rows + i * ldc, classes, vec, p, vec4);
+        class_row_load<T, CM>(rows + i * ldc, classes, ra.vec, p, ra.vec4);
         const int t = tr < classes ? tr : classes - 1;
         key = t * classes + first_argmax<CM>(p, classes);
       }
@@ -91,8 +68,6 @@ __global__ __launch_bounds__(CONF_THREADS) void class_confusion_ignore_kernel(co
   conf_table_store<CONF_THREADS>(table, classes * classes, partial);
 }
 
-struct ConfUpGeo { int H, W, lf; FastDiv divW, divH; };
-
 template <typename T> __device__ __forceinline__ float round_to_storage(float v) {
   if constexpr (sizeof(T) == 2) return bf16_to_f32(f32_to_bf16(v));      // (Elem<T>::store and load)
   else return v;
@@ -101,13 +76,12 @@ template <typename T> __device__ __forceinline__ float round_to_storage(float v)
 // one thread per (low-resolution cell (n, y0, x0), row jy of the cell): its f output pixels (y0 f + jy, x0 f + jx) share the four corner rows
 template <typename T, int CM>
 __global__ __launch_bounds__(256) void class_confusion_up_kernel(const T* __restrict__ low, const uint8_t* __restrict__ target, uint32_t items,
-                                                                 const ConfUpGeo g, int classes, int ldc, int* __restrict__ partial) {
+                                                                 const UpGeo g, int classes, int ldc, int* __restrict__ partial) {
   __shared__ int table[STP_MAX_CLASSES * STP_MAX_CLASSES];
   conf_table_clear<256>(table, classes * classes);
   const int f = 1 << g.lf;
   const float inv = 1.f / (float)f;
-  const bool vec = (ldc % Elem<T>::VEC) == 0 && CM % Elem<T>::VEC == 0;
-  const bool vec4 = !vec && sizeof(T) == 2 && (ldc % 4) == 0 && (CM % 4) == 0 && !(reinterpret_cast<uintptr_t>(low) & 7);
+  const RowAccess ra = row_access<T, CM>(low, ldc);
   for (uint32_t base = blockIdx.x * 256u; base < items; base += gridDim.x * 256u) {
     const uint32_t it = base + threadIdx.x;
     const bool on = it < items;
@@ -115,20 +89,14 @@ __global__ __launch_bounds__(256) void class_confusion_up_kernel(const T* __rest
     const uint8_t* trow = target;
     float fy = 0.f;
     if (on) {
-      const int jy = (int)(it & (uint32_t)(f - 1));
-      const uint32_t cell = it >> g.lf;
-      const uint32_t r = fdiv(cell, g.divW);
-      const int x0 = (int)(cell - r * (uint32_t)g.W);
-      const uint32_t n = fdiv(r, g.divH);
-      const int y0 = (int)(r - n * (uint32_t)g.H);
-      const int x1 = min(x0 + 1, g.W - 1), y1 = min(y0 + 1, g.H - 1);
-      fy = (float)jy * inv;
-      const T* b = low + (int64_t)n * g.H * g.W * ldc;
-      class_row_load<T, CM>(b + ((int64_t)y0 * g.W + x0) * ldc, classes, vec, v00, vec4);
-      class_row_load<T, CM>(b + ((int64_t)y0 * g.W + x1) * ldc, classes, vec, v01, vec4);
-      class_row_load<T, CM>(b + ((int64_t)y1 * g.W + x0) * ldc, classes, vec, v10, vec4);
-      class_row_load<T, CM>(b + ((int64_t)y1 * g.W + x1) * ldc, classes, vec, v11, vec4);
-      trow = target + (((int64_t)n * g.H + y0) * f + jy) * ((int64_t)g.W * f) + (int64_t)x0 * f;
+      const UpCell u = up_cell_decode(it, g, f);
+      fy = (float)u.jy * inv;
+      const T* b = low + (int64_t)u.n * g.H * g.W * ldc;
+      class_row_load<T, CM>(b + ((int64_t)u.y0 * g.W + u.x0) * ldc, classes, ra.vec, v00, ra.vec4);
+      class_row_load<T, CM>(b + ((int64_t)u.y0 * g.W + u.x1) * ldc, classes, ra.vec, v01, ra.vec4);
+      class_row_load<T, CM>(b + ((int64_t)u.y1 * g.W + u.x0) * ldc, classes, ra.vec, v10, ra.vec4);
+      class_row_load<T, CM>(b + ((int64_t)u.y1 * g.W + u.x1) * ldc, classes, ra.vec, v11, ra.vec4);
+      trow = up_cell_target_row(target, u, g, f);
     }
     for (int jx = 0; jx < f; ++jx) {
       int key = -1;
@@ -183,30 +151,10 @@ static inline void conf_finalize(const int* partial, int blocks, int classes, in
   hipLaunchKernelGGL(class_confusion_finalize_kernel, dim3((entries + 15) / 16), dim3(256), 0, s, partial, blocks, entries, counts);
 }
 
-extern "C" int stp_class_confusion(const void* rows, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype,
-                                   int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
-  const int rc = loss_check(dtype, rows && target && counts && workspace && pixels > 0 && pixels < (1ll << 31) && classes >= 2 &&
-                                       classes <= STP_MAX_CLASSES && ldc >= classes,
-                            workspace_bytes, classes >= 2 && classes <= STP_MAX_CLASSES ? conf_workspace_bytes(classes) : 0);
-  if (rc != STP_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t want = (pixels + CONF_THREADS - 1) / CONF_THREADS;
-  const int blocks = (int)(want > CONF_MAX_BLOCKS ? CONF_MAX_BLOCKS : want);
-  int* partial = (int*)workspace;
-  loss_by_dtype(dtype, [&](auto tag) {
-    using T = decltype(tag);
-    loss_by_class_bucket(classes, [&](auto bucket) {
-      constexpr int CM = decltype(bucket)::value;
-      hipLaunchKernelGGL((class_confusion_kernel<T, CM>), dim3(blocks), dim3(CONF_THREADS), 0, s, (const T*)rows, target, pixels, classes, ldc, partial);
-    });
-  });
-  conf_finalize(partial, blocks, classes, counts, s);
-  STP_LAUNCH_CHECK();
-  return STP_OK;
-}
-
-extern "C" int stp_class_confusion_ignore(const void* rows, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype,
-                                          int32_t* counts, void* workspace, size_t workspace_bytes, int32_t ignore_label, void* stream) {
+// both full-resolution entry points: stp_class_confusion passes ignore_label -1
+template <bool IGNORE>
+static int conf_entry(const void* rows, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype, int32_t* counts,
+                      void* workspace, size_t workspace_bytes, int32_t ignore_label, void* stream) {
   const int rc = loss_check(dtype, rows && target && counts && workspace && pixels > 0 && pixels < (1ll << 31) && classes >= 2 &&
                                        classes <= STP_MAX_CLASSES && ldc >= classes && ignore_label >= -1 && ignore_label <= 255,
                             workspace_bytes, classes >= 2 && classes <= STP_MAX_CLASSES ? conf_workspace_bytes(classes) : 0);
@@ -219,13 +167,23 @@ extern "C" int stp_class_confusion_ignore(const void* rows, const uint8_t* targe
     using T = decltype(tag);
     loss_by_class_bucket(classes, [&](auto bucket) {
       constexpr int CM = decltype(bucket)::value;
-      hipLaunchKernelGGL((class_confusion_ignore_kernel<T, CM>), dim3(blocks), dim3(CONF_THREADS), 0, s, (const T*)rows, target, pixels, classes, ldc,
+      hipLaunchKernelGGL((class_confusion_kernel<T, CM, IGNORE>), dim3(blocks), dim3(CONF_THREADS), 0, s, (const T*)rows, target, pixels, classes, ldc,
                          ignore_label, partial);
     });
   });
   conf_finalize(partial, blocks, classes, counts, s);
   STP_LAUNCH_CHECK();
   return STP_OK;
+}
+
+extern "C" int stp_class_confusion(const void* rows, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype,
+                                   int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+  return conf_entry<false>(rows, target, pixels, classes, ldc, dtype, counts, workspace, workspace_bytes, -1, stream);
+}
+
+extern "C" int stp_class_confusion_ignore(const void* rows, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype,
+                                          int32_t* counts, void* workspace, size_t workspace_bytes, int32_t ignore_label, void* stream) {
+  return conf_entry<true>(rows, target, pixels, classes, ldc, dtype, counts, workspace, workspace_bytes, ignore_label, stream);
 }
 
 extern "C" int stp_class_confusion_up_ok(int32_t factor, int32_t classes, int32_t dtype) {
@@ -244,8 +202,7 @@ extern "C" int stp_class_confusion_up(const void* low, const uint8_t* target, in
   if (workspace_bytes < conf_workspace_bytes(classes)) return STP_E_WORKSPACE;
   const int lf = factor == 2 ? 1 : factor == 4 ? 2 : factor == 8 ? 3 : 4;
   hipStream_t s = (hipStream_t)stream;
-  ConfUpGeo g;
-  g.H = H; g.W = W; g.lf = lf; g.divW = make_fastdiv((uint32_t)W); g.divH = make_fastdiv((uint32_t)H);
+  const UpGeo g = make_upgeo(H, W, lf);
   const int64_t items = ((int64_t)N * H * W) << lf;
   const int blocks = loss_grad_blocks(items, CONF_MAX_BLOCKS);
   int* partial = (int*)workspace;

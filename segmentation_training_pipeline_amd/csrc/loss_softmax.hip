@@ -16,11 +16,10 @@ __global__ __launch_bounds__(256) void softmax_loss_partial_kernel(const T* __re
   float a[LOSS_NSUM] = {0, 0, 0, 0, 0, 0, 0, 0};
   const int64_t per = (pixels + gridDim.x - 1) / gridDim.x;
   const int64_t i0 = (int64_t)blockIdx.x * per, i1 = i0 + per < pixels ? i0 + per : pixels;
-  const bool vec = (ldc % Elem<T>::VEC) == 0 && CM % Elem<T>::VEC == 0;
-  const bool vec4 = !vec && sizeof(T) == 2 && (ldc % 4) == 0 && (CM % 4) == 0 && !(reinterpret_cast<uintptr_t>(logits) & 7);
+  const RowAccess ra = row_access<T, CM>(logits, ldc);
   for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
     float p[CM];
-    softmax_row<T, CM>(logits + i * ldc, classes, vec, p, vec4);
+    softmax_row<T, CM>(logits + i * ldc, classes, ra.vec, p, ra.vec4);
     const int t = target[i] < classes ? target[i] : classes - 1;
     float pt, pmax, psum;
     softmax_row_stats(p, t, pt, pmax, psum);
@@ -47,11 +46,11 @@ __global__ __launch_bounds__(256) void softmax_loss_grad_kernel(const T* __restr
   constexpr int V = Elem<T>::VEC;
   const DiceIouGrad k(scalars);
   const float den = k.den, inv_den2 = k.inv_den2, num = k.num;
-  const bool vec = (ldc % V) == 0 && CM % V == 0, vout = (dlc % V) == 0;
-  const bool vec4 = !vec && sizeof(T) == 2 && (ldc % 4) == 0 && (CM % 4) == 0 && !(reinterpret_cast<uintptr_t>(logits) & 7);
+  const RowAccess ra = row_access<T, CM>(logits, ldc);
+  const bool vout = (dlc % V) == 0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pixels; i += (int64_t)gridDim.x * 256) {
     float p[CM];
-    softmax_row<T, CM>(logits + i * ldc, classes, vec, p, vec4);
+    softmax_row<T, CM>(logits + i * ldc, classes, ra.vec, p, ra.vec4);
     const int t = target[i] < classes ? target[i] : classes - 1;
     float pt = 0.f;
 #pragma unroll
@@ -131,8 +130,6 @@ __device__ __forceinline__ float cell_lanes_sum(float v, int lf) {
   return v;
 }
 
-struct UpGeo { int H, W, lf; FastDiv divW, divH; };
-
 // Row jy of cell (n, y0, x0): the logits of its f output pixels are L + D fx, fx = jx / f, with L / R the left / right corner columns
 // interpolated to the row FIRST (L = v00 + (v10 - v00) fy, R = v01 + (v11 - v01) fy, D = R - L): one multiply-add per class and pixel
 // instead of the three of the horizontal-first order of resize_bilinear_vec_kernel (the same number up to the rounding of fp32 sums,
@@ -142,25 +139,21 @@ __device__ __forceinline__ void up_row_load(const T* __restrict__ low, const uin
                                             int ldc, bool vec, bool vec4, float (&L)[CM], float (&D)[CM], uint32_t& tw0, uint32_t& tw1,
                                             uint32_t& tw2, uint32_t& tw3, float& fy, int& jy, uint32_t& cell) {
   const int f = 1 << g.lf;
-  jy = (int)(item & (uint32_t)(f - 1));
-  cell = item >> g.lf;
-  const uint32_t r = fdiv(cell, g.divW);
-  const int x0 = (int)(cell - r * (uint32_t)g.W);
-  const uint32_t n = fdiv(r, g.divH);
-  const int y0 = (int)(r - n * (uint32_t)g.H);
-  const int x1 = min(x0 + 1, g.W - 1), y1 = min(y0 + 1, g.H - 1);
+  const UpCell u = up_cell_decode(item, g, f);
+  jy = u.jy;
+  cell = u.cell;
   fy = (float)jy * (1.f / (float)f);
-  const T* b = low + (int64_t)n * g.H * g.W * ldc;
+  const T* b = low + (int64_t)u.n * g.H * g.W * ldc;
   float tmp[CM];
-  class_row_load<T, CM>(b + ((int64_t)y0 * g.W + x0) * ldc, classes, vec, L, vec4);
-  class_row_load<T, CM>(b + ((int64_t)y1 * g.W + x0) * ldc, classes, vec, tmp, vec4);
+  class_row_load<T, CM>(b + ((int64_t)u.y0 * g.W + u.x0) * ldc, classes, vec, L, vec4);
+  class_row_load<T, CM>(b + ((int64_t)u.y1 * g.W + u.x0) * ldc, classes, vec, tmp, vec4);
 #pragma unroll
   for (int c = 0; c < CM; ++c) L[c] = L[c] + (tmp[c] - L[c]) * fy;
-  class_row_load<T, CM>(b + ((int64_t)y0 * g.W + x1) * ldc, classes, vec, D, vec4);
-  class_row_load<T, CM>(b + ((int64_t)y1 * g.W + x1) * ldc, classes, vec, tmp, vec4);
+  class_row_load<T, CM>(b + ((int64_t)u.y0 * g.W + u.x1) * ldc, classes, vec, D, vec4);
+  class_row_load<T, CM>(b + ((int64_t)u.y1 * g.W + u.x1) * ldc, classes, vec, tmp, vec4);
 #pragma unroll
   for (int c = 0; c < CM; ++c) D[c] = (D[c] + (tmp[c] - D[c]) * fy) - L[c];
-  const uint8_t* trow = target + (((int64_t)n * g.H + y0) * f + jy) * ((int64_t)g.W * f) + (int64_t)x0 * f;
+  const uint8_t* trow = up_cell_target_row(target, u, g, f);
   tw0 = tw1 = tw2 = tw3 = 0u;
   if (f >= 4) {
     const uint32_t* tq = reinterpret_cast<const uint32_t*>(trow);
@@ -199,13 +192,12 @@ __global__ __launch_bounds__(256) void softmax_up_partial_kernel(const T* __rest
   float a[LOSS_NSUM] = {0, 0, 0, 0, 0, 0, 0, 0};
   const int f = 1 << g.lf;
   const float inv_f = 1.f / (float)f;
-  const bool vec = (ldc % Elem<T>::VEC) == 0 && CM % Elem<T>::VEC == 0;
-  const bool vec4 = !vec && sizeof(T) == 2 && (ldc % 4) == 0 && (CM % 4) == 0 && !(reinterpret_cast<uintptr_t>(low) & 7);
+  const RowAccess ra = row_access<T, CM>(low, ldc);
   for (uint32_t it = blockIdx.x * 256u + threadIdx.x; it < items; it += gridDim.x * 256u) {
     float L[CM], D[CM], fy;
     uint32_t tw0, tw1, tw2, tw3, cell;
     int jy;
-    up_row_load<T, CM>(low, target, it, g, classes, ldc, vec, vec4, L, D, tw0, tw1, tw2, tw3, fy, jy, cell);
+    up_row_load<T, CM>(low, target, it, g, classes, ldc, ra.vec, ra.vec4, L, D, tw0, tw1, tw2, tw3, fy, jy, cell);
     for (int jx = 0; jx < f; ++jx) {
       float e[CM], esum;
       const int t = up_pixel_exp<T, CM>(L, D, tw0, tw1, tw2, tw3, jx, inv_f, classes, e, esum);
@@ -229,14 +221,13 @@ __global__ __launch_bounds__(256) void softmax_up_grad_kernel(const T* __restric
   const float den = k.den, inv_den2 = k.inv_den2, num = k.num;
   const int f = 1 << g.lf;
   const float inv_f = 1.f / (float)f;
-  const bool vec = (ldc % Elem<T>::VEC) == 0 && CM % Elem<T>::VEC == 0;
-  const bool vec4 = !vec && sizeof(T) == 2 && (ldc % 4) == 0 && (CM % 4) == 0 && !(reinterpret_cast<uintptr_t>(low) & 7);
+  const RowAccess ra = row_access<T, CM>(low, ldc);
   // (items is a multiple of f and a cell's f lanes are lane-aligned: they enter and leave the loop together)
   for (uint32_t it = blockIdx.x * 256u + threadIdx.x; it < items; it += gridDim.x * 256u) {
     float L[CM], D[CM], fy;
     uint32_t tw0, tw1, tw2, tw3, cell;
     int jy;
-    up_row_load<T, CM>(low, target, it, g, classes, ldc, vec, vec4, L, D, tw0, tw1, tw2, tw3, fy, jy, cell);
+    up_row_load<T, CM>(low, target, it, g, classes, ldc, ra.vec, ra.vec4, L, D, tw0, tw1, tw2, tw3, fy, jy, cell);
     float A[CM], B[CM];                           // sum over the row of (1 - fx) g and fx g
 #pragma unroll
     for (int c = 0; c < CM; ++c) A[c] = B[c] = 0.f;
@@ -318,8 +309,7 @@ static void launch_softmax_up(const T* low, const uint8_t* target, int N, int H,
                               float* scalars, T* dl, int dlc, float grad_scale, const float* dev_scale, float* dev_record, float* partial,
                               float* corners, hipStream_t s) {
   const int64_t cells = (int64_t)N * H * W, items = cells << lf, pixels = items << lf;
-  UpGeo g;
-  g.H = H; g.W = W; g.lf = lf; g.divW = make_fastdiv((uint32_t)W); g.divH = make_fastdiv((uint32_t)H);
+  const UpGeo g = make_upgeo(H, W, lf);
   // value pass: at most 2048 partial rows (they fit the loss workspace), every thread the same number of rows where the count allows
   // (PSPNet's 589 824 rows: 1152 workgroups x 2 rows, not 1024 x 2.25)
   int64_t b = (items + 255) / 256;

@@ -1,5 +1,5 @@
 // Class rows of the multi-class (softmax) head held in registers: the row load, the per-pixel sums of the value passes and the padded
-// gradient row store, shared by the loss kernels of loss_softmax.hip and loss_softmax_ex.hip.
+// gradient row store, shared by the loss kernels of loss_softmax.hip and loss_softmax_ex.hip and the confusion kernels of class_confusion.hip.
 #pragma once
 #include "common.h"
 
@@ -39,6 +39,17 @@ __device__ __forceinline__ void class_row_load(const T* z, int classes, bool vec
 #pragma unroll
     for (int c = 0; c < CM; ++c) p[c] = c < classes ? Elem<T>::load(z + c) : 0.f;
   }
+}
+// The row access a KERNEL picks for class_row_load from the stride alone (the entry points that promise no base alignment): 16-byte
+// vectors when the stride and the class bucket are whole vectors, else 8-byte loads for 16-bit rows of 4 k elements on an 8-byte base.
+// (stp_softmax_loss_ex / _masked decide on the host, where the base's 16-byte alignment is tested too: smx_launch.)
+struct RowAccess { bool vec, vec4; };
+template <typename T, int CM>
+__device__ __forceinline__ RowAccess row_access(const T* base, int ldc) {
+  RowAccess r;
+  r.vec = (ldc % Elem<T>::VEC) == 0 && CM % Elem<T>::VEC == 0;
+  r.vec4 = !r.vec && sizeof(T) == 2 && (ldc % 4) == 0 && (CM % 4) == 0 && !(reinterpret_cast<uintptr_t>(base) & 7);
+  return r;
 }
 // logits in p[0 .. classes) -> probabilities (p[c] = 0 beyond `classes`)
 template <int CM>
@@ -123,7 +134,39 @@ __device__ __forceinline__ void softmax_grad_row_store(T* o, const float (&g)[CM
   }
 }
 
-// ---- the extended terms (loss_softmax_ex.hip, loss_softmax_masked.hip)
+// ---- class rows held at 1 / f of the mask's resolution (f = 2^lf; stp_softmax_cce_dice_up, stp_class_confusion_up): one work item per
+// (low-resolution cell (n, y0, x0), row jy of the cell) - its f output pixels (y0 f + jy, x0 f + jx) share the cell's four corner rows
+// (y0, x0), (y0, x1), (y1, x0), (y1, x1), x1 = min(x0 + 1, W - 1), y1 likewise.  Integer arithmetic only: each kernel interpolates in
+// its own order.
+struct UpGeo { int H, W, lf; FastDiv divW, divH; };
+static inline UpGeo make_upgeo(int H, int W, int lf) {
+  UpGeo g;
+  g.H = H; g.W = W; g.lf = lf; g.divW = make_fastdiv((uint32_t)W); g.divH = make_fastdiv((uint32_t)H);
+  return g;
+}
+struct UpCell {
+  int jy, y0, x0, x1, y1;
+  uint32_t cell, n;
+};
+// (f = 1 << g.lf, which every caller holds already)
+__device__ __forceinline__ UpCell up_cell_decode(uint32_t item, const UpGeo& g, int f) {
+  UpCell u;
+  u.jy = (int)(item & (uint32_t)(f - 1));
+  u.cell = item >> g.lf;
+  const uint32_t r = fdiv(u.cell, g.divW);
+  u.x0 = (int)(u.cell - r * (uint32_t)g.W);
+  u.n = fdiv(r, g.divH);
+  u.y0 = (int)(r - u.n * (uint32_t)g.H);
+  u.x1 = min(u.x0 + 1, g.W - 1);
+  u.y1 = min(u.y0 + 1, g.H - 1);
+  return u;
+}
+// the f target bytes of the item's row
+__device__ __forceinline__ const uint8_t* up_cell_target_row(const uint8_t* target, const UpCell& u, const UpGeo& g, int f) {
+  return target + (((int64_t)u.n * g.H + u.y0) * f + u.jy) * ((int64_t)g.W * f) + (int64_t)u.x0 * f;
+}
+
+// ---- the extended terms (loss_softmax_ex.hip)
 #define SMX_JACCARD_SMOOTH 100.f
 #define SMX_FOCAL_ALPHA 0.25f
 

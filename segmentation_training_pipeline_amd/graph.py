@@ -1398,33 +1398,28 @@ class Plan(object):
             return
         opts = self.masked_loss or {}
         ignore_label, class_weights = opts.get("ignore_label"), opts.get("class_weights")
-        if ignore_label is not None or class_weights is not None:
-            # one launch on the full-resolution logits, as under an extended spec: no low-resolution (_up) form, FPN / PSPNet keep
-            # their stp_resize_bilinear and its gradient launch.  The weights live in a plan-owned device tensor filled here.
-            if logits.C > 32:
-                raise StpShapeError("ignore_label / class_weights need a head of 2..32 classes")
-            ign = -1 if ignore_label is None else int(ignore_label)
-            cw = None
-            if class_weights is not None:
-                if len(class_weights) != logits.C:
-                    raise StpShapeError("class_weights: %d weights for %d classes" % (len(class_weights), logits.C))
-                cw = self._alloc((logits.C,), torch.float32)
-                cw.copy_(torch.tensor([float(w) for w in class_weights], dtype=torch.float32))
-            self.class_weights = cw
+        masked = ignore_label is not None or class_weights is not None
+        if masked or w_iou or w_jaccard or w_focal:
+            # one launch on the full-resolution logits: the extended loss, masked or not, has no low-resolution (_up) form, so FPN /
+            # PSPNet keep their stp_resize_bilinear and its gradient launch
+            name, tail, ign = "stp_softmax_loss_ex", (), None
+            if masked:
+                # the weights live in a plan-owned device tensor filled here
+                if logits.C > 32:
+                    raise StpShapeError("ignore_label / class_weights need a head of 2..32 classes")
+                ign = -1 if ignore_label is None else int(ignore_label)
+                cw = None
+                if class_weights is not None:
+                    if len(class_weights) != logits.C:
+                        raise StpShapeError("class_weights: %d weights for %d classes" % (len(class_weights), logits.C))
+                    cw = self._alloc((logits.C,), torch.float32)
+                    cw.copy_(torch.tensor([float(w) for w in class_weights], dtype=torch.float32))
+                self.class_weights = cw
+                name, tail = "stp_softmax_loss_masked", (ign, cw.data_ptr() if cw is not None else None)
             self.loss_scalars = self._alloc((16,), torch.float32)
             self.loss_scalars.zero_()
-            self._emit_loss("stp_softmax_loss_masked", logits, target, (logits.rows, logits.C, logits.C),
-                            (w_cce, w_dice, w_iou, w_jaccard, w_focal), tail=(ign, cw.data_ptr() if cw is not None else None))
+            self._emit_loss(name, logits, target, (logits.rows, logits.C, logits.C), (w_cce, w_dice, w_iou, w_jaccard, w_focal), tail=tail)
             self._emit_confusion(logits, target, ignore_label=ign)
-            logits.grad_ready = self.training
-            return
-        if w_iou or w_jaccard or w_focal:
-            # one launch on the full-resolution logits: the extended loss has no low-resolution (_up) form, so FPN / PSPNet keep
-            # their stp_resize_bilinear and its gradient launch
-            self.loss_scalars = self._alloc((16,), torch.float32)
-            self.loss_scalars.zero_()
-            self._emit_loss("stp_softmax_loss_ex", logits, target, (logits.rows, logits.C, logits.C), (w_cce, w_dice, w_iou, w_jaccard, w_focal))
-            self._emit_confusion(logits, target)
             logits.grad_ready = self.training
             return
         self.loss_scalars = self._alloc((12,), torch.float32)

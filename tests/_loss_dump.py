@@ -1,6 +1,7 @@
 """Outputs of every loss entry point on seeded inputs, as files (helper in the style of tests/_plan_dump.py; not collected): the
 scalars, the gradient tensor and the bias gradient (where one exists) of the seven launches of ``Plan.LOSS_LAUNCHES`` plus
-``stp_softmax_cce_dice_up``, ``stp_sigmoid_loss_bias_grad`` and ``stp_sigmoid_multilabel_bias_grad``, in fp32, bf16 and fp16.  The
+``stp_softmax_cce_dice_up``, ``stp_sigmoid_loss_bias_grad`` and ``stp_sigmoid_multilabel_bias_grad``, the masked softmax loss
+(``stp_softmax_loss_masked``) and the counts of ``stp_class_confusion`` / ``stp_class_confusion_ignore``, in fp32, bf16 and fp16.  The
 loss kernels promise a fixed order of additions, so two builds of the library that compute the same thing give the same BYTES: run
 
     python tests/_loss_dump.py OUT_A
@@ -16,7 +17,10 @@ The sizes are the smallest that reach every path of the shared reduction (csrc/l
     50 x 1024 + 5      50 value workgroups: the four-in-flight loop of the 16-wide finalize, with a remainder
     230 x 1024 + 77    230 value workgroups: the eight-in-flight loop of the 8-wide finalize, with a remainder
     1 100 000          more than 4096 x 256 work items: a second trip of the capped gradient grid
-Softmax families: 3 classes at every size, 5 / 20 / 32 at two; multi-label: 3 at every size, 8 at two."""
+Softmax families: 3 classes at every size, 5 / 20 / 32 at two; multi-label: 3 at every size, 8 at two.
+
+``python tests/_loss_dump.py --time`` (under the same two variables) prints instead the median time per call of
+``stp_softmax_loss_ex``, ``stp_softmax_loss_masked``, ``stp_class_confusion`` and ``stp_class_confusion_ignore``."""
 import os
 import sys
 
@@ -175,14 +179,98 @@ def up_family(d, tag, dtype):
                 d.save("softmax_cce_dice_up.%s.c%d.f%d.%s" % (tag, classes, f, vname), scalars=s, grad=dlow, record=rec)
 
 
+def _ignored(t, n, seed):
+    """``t`` with 255 in a seeded 30 % of its pixels"""
+    return torch.where((torch.rand(n, generator=_gen(seed)) < 0.3).to(DEV), torch.full_like(t, 255), t)
+
+
+def masked_family(d, tag, dtype):
+    """stp_softmax_loss_masked: the sizes and classes of class_families; ignore label 255 / none (-1) x spread class weights / NULL,
+    and every pixel ignored at 4097"""
+    for classes, sizes in ((3, SIZES), (5, SIZES_MORE_CLASSES), (20, SIZES_MORE_CLASSES), (32, SIZES_MORE_CLASSES)):
+        spread = (0.5 + 0.25 * torch.arange(classes, dtype=torch.float32)).to(DEV)
+        for n in sizes:
+            z = _logits(n + classes, n, classes, dtype)
+            t = _ignored(torch.randint(0, classes, (n,), generator=_gen(n + 7), dtype=torch.int64).to(torch.uint8).to(DEV), n, n + 11)
+            dlc = _padded(classes, dtype)
+            cases = [("ign255.cw", t, 255, spread), ("ign255.nocw", t, 255, None), ("noign.cw", t, -1, spread), ("noign.nocw", t, -1, None)]
+            if n == 4097:
+                cases.append(("allignored.cw", torch.full_like(t, 255), 255, spread))
+            for cname, tt, ign, cw in cases:
+                for vname, w5 in [("w5", W5)] + ([("w5first2", W5_FIRST_TWO)] if n == 4097 else []):
+                    s = torch.zeros(16, dtype=torch.float32, device=DEV)
+                    dl = torch.zeros(n, dlc, dtype=dtype, device=DEV)
+                    keep, addr = _weights(w5)
+                    d.call("stp_softmax_loss_masked", z.data_ptr(), tt.data_ptr(), n, classes, classes, ops.dt(z), addr, s.data_ptr(), dl.data_ptr(),
+                           dlc, 2.0, d.ws.data_ptr(), d.ws.numel() * 4, ign, ops.ptr(cw))
+                    d.save("softmax_loss_masked.%s.c%d.%d.%s.%s" % (tag, classes, n, cname, vname), scalars=s, grad=dl)
+
+
+CONF_SIZES = (5 * 1024 + 77, 600000)      # the second: past 512 workgroups x 1024 pixels, a second trip of the capped grid
+
+
+def _confusion_ws(classes):
+    nb = int(_lib.load().stp_class_confusion_workspace_bytes(classes))
+    return torch.zeros(nb // 4, dtype=torch.int32, device=DEV), nb
+
+
+def confusion_family(d, tag, dtype):
+    """stp_class_confusion and stp_class_confusion_ignore (label 255, and -1): the int32 counts"""
+    for classes in (3, 20, 32):
+        ws, nb = _confusion_ws(classes)
+        for n in CONF_SIZES:
+            rows = _logits(n + 3 * classes, n, classes, dtype)
+            targets = (("runs", (torch.arange(n) // 97 % classes).to(torch.uint8).to(DEV)),
+                       ("random", torch.randint(0, classes, (n,), generator=_gen(n + 13), dtype=torch.int64).to(torch.uint8).to(DEV)))
+            for tname, t in targets:
+                t = _ignored(t, n, n + 17)
+                for name, tail in (("class_confusion", ()), ("class_confusion_ignore", (255,)), ("class_confusion_ignore", (-1,))):
+                    counts = torch.zeros(classes * classes, dtype=torch.int32, device=DEV)
+                    d.call("stp_" + name, rows.data_ptr(), t.data_ptr(), n, classes, classes, ops.dt(rows), counts.data_ptr(), ws.data_ptr(), nb, *tail)
+                    d.save("%s.%s.c%d.%d.%s%s" % (name, tag, classes, n, tname, "".join(".ign%d" % v for v in tail)), counts=counts)
+
+
+def time_calls(warmup=10, calls=50):
+    """--time: the median device-event time per call of the two extended softmax losses (with gradient, W5) and the two full-resolution
+    confusion counts, at sizes a user runs"""
+    for tag, storage, dtype, classes, n, ldc in (("bf16", "bf16", torch.bfloat16, 20, 8 * 768 * 768, 24), ("fp16", "fp16", torch.float16, 3, 4 * 1024 * 1024, 8)):
+        with _lib.storage(storage):
+            z = _logits(classes, n, ldc, dtype)
+            t = _ignored(torch.randint(0, classes, (n,), generator=_gen(7), dtype=torch.int64).to(torch.uint8).to(DEV), n, 11)
+            cw = (0.5 + 0.25 * torch.arange(classes, dtype=torch.float32)).to(DEV)
+            s = torch.zeros(16, dtype=torch.float32, device=DEV)
+            dl = torch.zeros(n, ldc, dtype=dtype, device=DEV)
+            lws = torch.zeros(ops.loss_workspace_bytes() // 4, dtype=torch.float32, device=DEV)
+            counts = torch.zeros(classes * classes, dtype=torch.int32, device=DEV)
+            cws, nb = _confusion_ws(classes)
+            keep, addr = _weights(W5)
+            loss = (z.data_ptr(), t.data_ptr(), n, classes, ldc, ops.dt(z), addr, s.data_ptr(), dl.data_ptr(), ldc, 2.0, lws.data_ptr(), lws.numel() * 4)
+            conf = (z.data_ptr(), t.data_ptr(), n, classes, ldc, ops.dt(z), counts.data_ptr(), cws.data_ptr(), nb)
+            for name, args in (("stp_softmax_loss_ex", loss), ("stp_softmax_loss_masked", loss + (255, cw.data_ptr())),
+                               ("stp_class_confusion", conf), ("stp_class_confusion_ignore", conf + (255,))):
+                ms = []
+                for k in range(warmup + calls):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    _lib.call(name, *args, ops.stream())
+                    e1.record()
+                    e1.synchronize()
+                    if k >= warmup:
+                        ms.append(e0.elapsed_time(e1))
+                print("time %-28s %s c%d %d px stride %d  median %.1f us  (min %.1f)" % (name, tag, classes, n, ldc, 1e3 * float(np.median(ms)), 1e3 * min(ms)),
+                      flush=True)
+
+
 def main(argv):
+    if argv and argv[0] == "--time":
+        return time_calls()
     out_dir = argv[0]
     os.makedirs(out_dir, exist_ok=True)
     total = 0
     for tag, storage, dtype in DTYPES:
         with _lib.storage(storage):
             d = Dump(out_dir)
-            for family in (sigmoid_families, class_families, multilabel_family, up_family):
+            for family in (sigmoid_families, class_families, multilabel_family, up_family, masked_family, confusion_family):
                 family(d, tag, dtype)
             total += d.count
             print("%s  %d files" % (tag, d.count), flush=True)
