@@ -899,6 +899,47 @@ size_t stp_threshold_counts_workspace_bytes(int32_t T);
 int stp_threshold_counts(const float* map, const uint8_t* target, int32_t h, int32_t w, int32_t C, int32_t channel, const float* thresholds,
                          int32_t T, int64_t* counts, int64_t* totals, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Connected components on the device (csrc/components.hip): the objects of ONE uint8 mask [h][w] - what scipy.ndimage.label and
+ * skimage's remove_small_objects / remove_small_holes compute - and the run-length code of a label image, one triple per run
+ * (segmentation_pipeline/impl/rle.py: multi_rle_encode).  uint8, int32 and int64 only (both builds export the same code); exact integer
+ * work, equal to the host statement (tests/_components_reference.py) bit for bit and from run to run.  Only integer atomics (atomicMin on
+ * the union-find's parents, atomicAdd on the areas); no workgroup waits for another.  The rules of the mask entries hold: STP_E_BADARG
+ * before any launch for a NULL pointer, a size <= 0 and what each entry lists; never a synchronisation or an allocation; h * w < 2^31;
+ * workspace 8-byte aligned and >= the entry's *_workspace_bytes(h, w) (0 for sizes it refuses), else STP_E_WORKSPACE.
+ *
+ *   stp_mask_label       : foreground = (img[y][x] != 0) != (invert != 0).  labels[y * w + x] = 0 off the foreground, else the number
+ *                          1..*count of the pixel's component under the 4-neighbourhood (connectivity 1) or the 8-neighbourhood (2);
+ *                          components are numbered by their first pixel in row-major order:  root = the smallest pixel index y * w + x
+ *                          of the component, label = the number of roots at or before it.  This is scipy.ndimage.label(fg,
+ *                          generate_binary_structure(2, connectivity)).  Every cell of `labels` and *count are written (int32, device).
+ *                          BADARG: connectivity outside 1..2.
+ *   stp_mask_area_filter : area(c) = the pixel count of foreground component c.  invert 0: dst = (src != 0) with the pixels of every
+ *                          component of area < min_size cleared (skimage's remove_small_objects(mask, min_size, connectivity): label,
+ *                          bincount, sizes < min_size - a strict <).  invert 1, foreground = the ZERO pixels: dst = (src != 0) with the
+ *                          pixels of every zero component of area < min_size set (remove_small_holes(mask, area_threshold = min_size,
+ *                          connectivity) = ~remove_small_objects(~mask, ...): a small zero component at the image border is filled
+ *                          too).  dst is uint8 {0, 1}; min_size = 0 (and 1) gives the binarised source.  src == dst is allowed: the
+ *                          FIRST launch is the only one that reads src (it turns it into the parent array: >= 0 on the foreground), the
+ *                          LAST is the only one that writes dst, and the one-launch form for min_size <= 1 reads and writes a pixel in
+ *                          one thread.  BADARG: connectivity outside 1..2, min_size < 0.
+ *   stp_label_rle        : the column-major numbering of stp_mask_rle (1-based x * h + y + 1) on an int32 image with values >= 0 (any
+ *                          such image, not only stp_mask_label's).  A run is a maximal stretch of EQUAL NON-ZERO values of the flat
+ *                          column-major array: a stretch that leaves the bottom of a column and goes on at the top of the next with the
+ *                          same value is one run, with another value two.  runs[k] = (value, start, length) int32 triples for
+ *                          k < *count in ascending start; triples past *count are not written.  capacity (triples `runs` holds) >=
+ *                          h * w, the most a label image can have, else BADARG.  The triples of one value, in order, are the runs of
+ *                          rle_encode(labels == value). */
+size_t stp_mask_label_workspace_bytes(int32_t h, int32_t w);
+int stp_mask_label(const uint8_t* img, int32_t h, int32_t w, int32_t connectivity, int32_t invert, int32_t* labels, int32_t* count,
+                   void* workspace, size_t workspace_bytes, void* stream);
+size_t stp_mask_area_filter_workspace_bytes(int32_t h, int32_t w);
+int stp_mask_area_filter(const uint8_t* src, uint8_t* dst, int32_t h, int32_t w, int32_t connectivity, int32_t invert, int64_t min_size,
+                         void* workspace, size_t workspace_bytes, void* stream);
+size_t stp_label_rle_workspace_bytes(int32_t h, int32_t w);
+int stp_label_rle(const int32_t* labels, int32_t h, int32_t w, int32_t* runs, int32_t* count, int64_t capacity, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

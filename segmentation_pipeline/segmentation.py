@@ -389,7 +389,7 @@ class PipelineConfig(generic.GenericTaskConfig):
     def _softmax_head(self):
         return self.classes > 1 and self.all.get("activation") != "sigmoid"
 
-    def _mask_mode(self, threshold, opening, closing, channel):
+    def _mask_mode(self, threshold, opening, closing, channel, min_size=0, area_threshold=0):
         """stp_mask_threshold's mode for this head (0: sigmoid map > threshold, 1: softmax argmax == channel), after the argument checks
         every mask method makes before a model is loaded."""
         if not 0 <= int(channel) < int(self.classes):
@@ -397,15 +397,20 @@ class PipelineConfig(generic.GenericTaskConfig):
         for name, r in (("opening", opening), ("closing", closing)):
             if int(r) != r or not 0 <= r <= 7:
                 raise ValueError("%s is the radius of a disk, 0 (off) to 7: got %r" % (name, r))
+        for name, v in (("min_size", min_size), ("area_threshold", area_threshold)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError("%s is a pixel count, an integer >= 0 (0: off): got %r" % (name, v))
         if self._softmax_head():
             if threshold != 0.5:
                 raise ValueError("a softmax head has one label per pixel: the mask of `channel` is argmax == channel and takes no threshold")
             return 1
         return 0
 
-    def _device_mask(self, probs, mode, threshold, opening, closing, channel):
+    def _device_mask(self, probs, mode, threshold, opening, closing, channel, min_size=0, area_threshold=0):
         """One image's finished device map [h, w, classes] -> its uint8 {0, 1} device mask [h, w]: stp_mask_threshold, then the disk
-        opening (erode, dilate), then the disk closing (dilate, erode) - scipy.ndimage's binary_opening / binary_closing with defaults."""
+        opening (erode, dilate), then the disk closing (dilate, erode) - scipy.ndimage's binary_opening / binary_closing with defaults -,
+        then stp_mask_area_filter in place: skimage's remove_small_objects(min_size), remove_small_holes(area_threshold), connectivity
+        1.  A step whose argument is 0 launches nothing."""
         from segmentation_training_pipeline_amd import ops
         import torch
         h, w, C = (int(v) for v in probs.shape)
@@ -417,6 +422,11 @@ class PipelineConfig(generic.GenericTaskConfig):
                 if r:
                     ops.mask_morph(a, b, h, w, r, first)
                     ops.mask_morph(b, a, h, w, r, 1 - first)
+        if min_size or area_threshold:
+            ws = torch.empty(ops.mask_area_filter_workspace_bytes(h, w), dtype=torch.uint8, device=probs.device)
+            for size, invert in ((min_size, 0), (area_threshold, 1)):
+                if size:
+                    ops.mask_area_filter(a, a, h, w, 1, invert, size, ws)
         return a
 
     @staticmethod
@@ -433,38 +443,93 @@ class PipelineConfig(generic.GenericTaskConfig):
         n = int(count.item())
         return " ".join(map(str, runs[:n].reshape(-1).cpu().numpy().tolist()))      # "start length start length ..."
 
+    @staticmethod
+    def _device_labels(mask):
+        """-> (int32 device label image [h, w], count): the 8-connected components of a device mask in scipy's / skimage's numbering
+        (stp_mask_label, connectivity 2)."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        h, w = (int(v) for v in mask.shape)
+        labels = torch.empty((h, w), dtype=torch.int32, device=mask.device)
+        count = torch.empty(1, dtype=torch.int32, device=mask.device)
+        ws = torch.empty(ops.mask_label_workspace_bytes(h, w), dtype=torch.uint8, device=mask.device)
+        ops.mask_label(mask, h, w, 2, 0, labels, count, ws)
+        return labels, count
+
+    @staticmethod
+    def _group_runs(runs, count):
+        """(value, start, length) triples in ascending start -> one ``"start length ..."`` string per value 1..count: a stable sort by
+        value keeps each value's runs in order."""
+        runs = np.asarray(runs).reshape(-1, 3)
+        runs = runs[np.argsort(runs[:, 0], kind="stable")]
+        cuts = np.searchsorted(runs[:, 0], np.arange(1, count + 2))
+        return [" ".join(map(str, runs[cuts[k]:cuts[k + 1], 1:].reshape(-1).tolist())) for k in range(count)]
+
+    @classmethod
+    def _device_multi_rle(cls, mask):
+        """impl.rle.multi_rle_encode of a device mask: stp_mask_label (connectivity 2), stp_label_rle, then the two counts and the first
+        ``runs`` triples come back and are grouped by label on the host."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        h, w = (int(v) for v in mask.shape)
+        labels, count = cls._device_labels(mask)
+        runs = torch.empty((h * w, 3), dtype=torch.int32, device=mask.device)
+        nruns = torch.empty(1, dtype=torch.int32, device=mask.device)
+        ws = torch.empty(ops.label_rle_workspace_bytes(h, w), dtype=torch.uint8, device=mask.device)
+        ops.label_rle(labels, h, w, runs, nruns, ws)
+        n, k = int(count.item()), int(nruns.item())
+        return cls._group_runs(runs[:k].cpu().numpy(), n)
+
     def predict_masks(self, spath, fold=0, stage=0, limit=-1, ttflips=False, threshold=0.5, opening=0, closing=0, channel=0, rle=True):
         """README.md:498-525 without the host: a generator of ``(file_name, rle_string)`` - or, ``rle=False``, ``(file_name, uint8 h x w
         mask)`` - per image of ``spath``.  Per image, on the device: the finished map at the image's own size (``fold`` may be a list,
         ``ttflips`` and ``crops:`` as in ``predict_in_directory``), ``map[..., channel] > float32(threshold)`` (a softmax head: ``argmax
         == channel``, no threshold), a disk(``opening``) opening, a disk(``closing``) closing (radius 0: off; both as
         scipy.ndimage's binary_opening / binary_closing with defaults - that closing clears a band at the image border), the
-        run-length code.  Only the runs (or the mask) come back.  Connected-component clean-up (remove_small_objects,
-        remove_small_holes, multi_rle_encode) stays host code on the ``rle=False`` masks."""
-        mode = self._mask_mode(threshold, opening, closing, channel)      # (refusals fire here, not at the first next())
+        run-length code.  Only the runs (or the mask) come back.  Connected-component clean-up and per-object codes
+        (remove_small_objects, remove_small_holes, multi_rle_encode) are ``predict_masks_ex``: this method with three more keywords."""
+        return self.predict_masks_ex(spath, fold, stage, limit, ttflips, threshold, opening, closing, channel, rle)
+
+    def predict_masks_ex(self, spath, fold=0, stage=0, limit=-1, ttflips=False, threshold=0.5, opening=0, closing=0, channel=0, rle=True,
+                         min_size=0, area_threshold=0, components=False):
+        """``predict_masks`` (same arguments, same launches when the three new keywords keep their defaults) with the README's
+        connected-component steps on the device: after the closing, skimage's ``remove_small_objects(mask, min_size)`` and then
+        ``remove_small_holes(mask, area_threshold)`` (integers >= 0, 0: off; connectivity 1, skimage's default; README.md:498-525
+        uses 64 and 64), then the run-length code.  ``components=True`` splits the final mask into its 8-connected objects:
+        ``(file_name, [rle_string, ...])``, one string per object in label order - exactly
+        ``impl.rle.multi_rle_encode(mask[:, :, None])``, ``[]`` for an empty mask - or, ``rle=False``, ``(file_name, int32 h x w label
+        image)`` in scipy.ndimage.label's numbering.  Only the runs (or the mask, or the labels) come back."""
+        mode = self._mask_mode(threshold, opening, closing, channel, min_size, area_threshold)      # (refusals fire here, not at the first next())
 
         def masks():
             for items, maps in self._predict_batches(spath, fold, stage, limit, ttflips, self.PROBS, device=True):
                 for it, probs in zip(items, maps):
-                    mask = self._device_mask(probs, mode, float(threshold), int(opening), int(closing), int(channel))
-                    yield it.id, (self._device_rle(mask) if rle else mask.cpu().numpy())
+                    mask = self._device_mask(probs, mode, float(threshold), int(opening), int(closing), int(channel), int(min_size),
+                                             int(area_threshold))
+                    if components:
+                        yield it.id, (self._device_multi_rle(mask) if rle else self._device_labels(mask)[0].cpu().numpy())
+                    else:
+                        yield it.id, (self._device_rle(mask) if rle else mask.cpu().numpy())
         return masks()
 
     def predict_to_csv(self, spath, csv_path, fold=0, stage=0, limit=-1, ttflips=False, threshold=0.5, opening=0, closing=0, channel=0,
-                       columns=("image", "rle_mask")):
-        """README.md:498-525 in one call: ``predict_masks`` written as a CSV with the header ``columns``; the image column holds the file
-        name up to its first ``.``.  Returns the number of rows."""
+                       columns=("image", "rle_mask"), min_size=0, area_threshold=0, components=False):
+        """README.md:498-525 in one call: ``predict_masks_ex`` written as a CSV with the header ``columns``; the image column holds the file
+        name up to its first ``.``.  ``components=True``: one row per object, the image name repeated; an image without objects gets
+        one row with an empty code.  Returns the number of rows."""
         import csv
         if len(columns) != 2:
             raise ValueError("columns names the image column and the run-length column")
-        rows = self.predict_masks(spath, fold, stage, limit, ttflips, threshold, opening, closing, channel)
+        rows = self.predict_masks_ex(spath, fold, stage, limit, ttflips, threshold, opening, closing, channel, True, min_size, area_threshold,
+                                     components)
         n = 0
         with open(csv_path, "w", newline="") as f:
             out = csv.writer(f, lineterminator="\n")
             out.writerow(list(columns))
             for name, code in rows:
-                out.writerow([name[0:name.index(".")] if "." in name else name, code])
-                n += 1
+                for c in ((code or [""]) if components else [code]):
+                    out.writerow([name[0:name.index(".")] if "." in name else name, c])
+                    n += 1
         return n
 
     @staticmethod

@@ -220,6 +220,12 @@ SIGNATURES = {
     "stp_mask_rle": (i32, [vp, i32, i32, vp, vp, i64, vp, sz, vp]),
     "stp_threshold_counts_workspace_bytes": (sz, [i32]),
     "stp_threshold_counts": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(f32), i32, vp, vp, vp, sz, vp]),
+    "stp_mask_label_workspace_bytes": (sz, [i32, i32]),
+    "stp_mask_label": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "stp_mask_area_filter_workspace_bytes": (sz, [i32, i32]),
+    "stp_mask_area_filter": (i32, [vp, vp, i32, i32, i32, i32, i64, vp, sz, vp]),
+    "stp_label_rle_workspace_bytes": (sz, [i32, i32]),
+    "stp_label_rle": (i32, [vp, i32, i32, vp, vp, i64, vp, sz, vp]),
 }
 
 _libs = {}          # storage format ("bf16" | "fp16") -> loaded library

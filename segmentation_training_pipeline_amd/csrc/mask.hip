@@ -13,6 +13,7 @@
 //   stp_threshold_counts  per pixel j = #thresholds below the value, a workgroup LDS table [T + 1][2] of integers (wave peel of
 //                         wave_count.h), workgroup tables summed and suffix-summed by a finalize launch
 #include "common.h"
+#include "rle_scan.h"
 #include "wave_count.h"
 
 static inline bool mask_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -170,8 +171,6 @@ extern "C" int stp_mask_morph(const uint8_t* src, uint8_t* dst, int32_t h, int32
 // and a column's last word has nb = h - 64 (HW - 1) valid bits.  A run starts at a 1 whose flat predecessor is 0 (or missing) and ends at a
 // 1 whose flat successor is 0 (or missing); the k-th end closes the k-th start, and the start of a run is the last start at or before its
 // end - inside the end's word, or carried: the largest start position of the words before it.
-#define RLE_THREADS 256
-
 struct RleGeo {
   int h, HW, nb_last;      // nb_last: valid bits of a column's last word
   int64_t words;           // w * HW
@@ -216,27 +215,6 @@ __device__ __forceinline__ void rle_word_edges(const unsigned long long* __restr
   e = v & ~((v >> 1) | (next << (nb - 1)));
 }
 
-// over the workgroup's 256 threads: the exclusive sum of `a` and the exclusive maximum of `m` (-1 for thread 0), and both totals
-__device__ __forceinline__ void rle_block_scan(int a, int m, int (&sa)[RLE_THREADS], int (&sm)[RLE_THREADS], int& excl_sum, int& excl_max,
-                                               int& total_sum, int& total_max) {
-  const int t = threadIdx.x;
-  sa[t] = a;
-  sm[t] = m;
-  __syncthreads();
-  for (int off = 1; off < RLE_THREADS; off <<= 1) {
-    const int xa = t >= off ? sa[t - off] : 0, xm = t >= off ? sm[t - off] : -1;
-    __syncthreads();
-    sa[t] += xa;
-    sm[t] = max(sm[t], xm);
-    __syncthreads();
-  }
-  excl_sum = sa[t] - a;
-  excl_max = t > 0 ? sm[t - 1] : -1;
-  total_sum = sa[RLE_THREADS - 1];
-  total_max = sm[RLE_THREADS - 1];
-  __syncthreads();      // (the arrays are free again)
-}
-
 // per workgroup of 256 words: how many runs end in it, and the position of its last run start (-1: none)
 __global__ __launch_bounds__(RLE_THREADS) void rle_count_kernel(const unsigned long long* __restrict__ words, const RleGeo g,
                                                                 int* __restrict__ block_ends, int* __restrict__ block_last) {
@@ -251,26 +229,6 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_count_kernel(const unsigned l
     block_ends[blockIdx.x] = ts;
     block_last[blockIdx.x] = tm;
   }
-}
-
-// one workgroup, the blocks in order: ends_before[b] = runs that end before block b, carry[b] = the last run start before it; *count
-__global__ __launch_bounds__(RLE_THREADS) void rle_scan_kernel(const int* __restrict__ block_ends, const int* __restrict__ block_last, int blocks,
-                                                               int* __restrict__ ends_before, int* __restrict__ carry, int* __restrict__ count) {
-  __shared__ int sa[RLE_THREADS], sm[RLE_THREADS];
-  int run_sum = 0, run_max = -1;
-  for (int b0 = 0; b0 < blocks; b0 += RLE_THREADS) {
-    const int b = b0 + threadIdx.x;
-    const int a = b < blocks ? block_ends[b] : 0, m = b < blocks ? block_last[b] : -1;
-    int es, em, ts, tm;
-    rle_block_scan(a, m, sa, sm, es, em, ts, tm);
-    if (b < blocks) {
-      ends_before[b] = run_sum + es;
-      carry[b] = max(run_max, em);
-    }
-    run_sum += ts;
-    run_max = max(run_max, tm);
-  }
-  if (threadIdx.x == 0) *count = run_sum;
 }
 
 __global__ __launch_bounds__(RLE_THREADS) void rle_write_kernel(const unsigned long long* __restrict__ words, const RleGeo g,

@@ -428,3 +428,47 @@ def threshold_counts(probs, target, h, w, Cn, channel, thresholds, counts, total
     thr = (C.c_float * max(T, 1))(*[float(t) for t in thresholds])
     _lib.call("stp_threshold_counts", ptr(_dev(probs)), ptr(_dev(target)), h, w, Cn, int(channel), thr, T, ptr(_dev(counts)), ptr(_dev(totals)),
               ptr(_dev(workspace)), workspace.numel() * workspace.element_size(), stream())
+
+
+# connected components on the device (csrc/components.hip): ONE uint8 mask [h, w] -> its label image, its area-filtered mask, label runs
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def mask_label_workspace_bytes(h, w):
+    return int(_lib.load().stp_mask_label_workspace_bytes(h, w))
+
+
+def mask_label(img, h, w, connectivity, invert, labels, count, workspace):
+    """``labels`` int32 [h, w] = scipy.ndimage.label of ``(img != 0) != invert`` (connectivity 1: 4-, 2: 8-neighbourhood), ``count`` int32 [1]."""
+    if (img.numel() < h * w or labels.numel() < h * w or img.dtype != torch.uint8 or labels.dtype != torch.int32 or count.dtype != torch.int32
+            or count.numel() < 1):
+        raise ValueError("mask_label: a uint8 image and int32 labels of h x w, an int32 count")
+    _lib.call("stp_mask_label", ptr(_dev(img)), h, w, int(connectivity), int(invert), ptr(_dev(labels)), ptr(_dev(count)),
+              ptr(_dev(workspace)), _nbytes(workspace), stream())
+
+
+def mask_area_filter_workspace_bytes(h, w):
+    return int(_lib.load().stp_mask_area_filter_workspace_bytes(h, w))
+
+
+def mask_area_filter(src, dst, h, w, connectivity, invert, min_size, workspace):
+    """``dst`` uint8 {0, 1} = ``src != 0`` without its components of fewer than ``min_size`` pixels (invert 0: remove_small_objects) or with
+    its zero components of fewer than ``min_size`` pixels set (invert 1: remove_small_holes); ``dst`` may be ``src``."""
+    if min(src.numel(), dst.numel()) < h * w or src.dtype != torch.uint8 or dst.dtype != torch.uint8:
+        raise ValueError("mask_area_filter: two uint8 buffers of h x w")
+    _lib.call("stp_mask_area_filter", ptr(_dev(src)), ptr(_dev(dst)), h, w, int(connectivity), int(invert), int(min_size),
+              ptr(_dev(workspace)), _nbytes(workspace), stream())
+
+
+def label_rle_workspace_bytes(h, w):
+    return int(_lib.load().stp_label_rle_workspace_bytes(h, w))
+
+
+def label_rle(labels, h, w, runs, count, workspace):
+    """``runs`` int32 [capacity, 3] = (value, start, length) of the column-major runs of equal non-zero values of the int32 image ``labels``
+    [h, w], ``count`` int32 [1]."""
+    if labels.numel() < h * w or labels.dtype != torch.int32 or runs.dtype != torch.int32 or count.dtype != torch.int32 or count.numel() < 1:
+        raise ValueError("label_rle: an int32 image of h x w, int32 runs and count")
+    _lib.call("stp_label_rle", ptr(_dev(labels)), h, w, ptr(_dev(runs)), ptr(_dev(count)), runs.numel() // 3, ptr(_dev(workspace)),
+              _nbytes(workspace), stream())
