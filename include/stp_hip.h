@@ -940,6 +940,45 @@ size_t stp_label_rle_workspace_bytes(int32_t h, int32_t w);
 int stp_label_rle(const int32_t* labels, int32_t h, int32_t w, int32_t* runs, int32_t* count, int64_t capacity, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Object-level matching of two label images on the device (csrc/object_match.hip): the counters of the per-object competition scores
+ * (Airbus ship detection: F2 over IoU thresholds; DSB-2018: TP / (TP + FP + FN)).  int32 and int64 only (both builds export the same
+ * code); no float arithmetic; exact integer work, equal to the host statement (tests/_object_match_reference.py) and byte-identical from
+ * run to run.  Only integer atomics (a 64-bit atomicCAS on a table key whose return value decides, atomicAdd on counts, areas and
+ * counters); no workgroup waits for another.  The rules of the component entries hold: STP_E_BADARG before any launch for a NULL pointer,
+ * a size <= 0 and what is listed below; never a synchronisation or an allocation; h * w < 2^31; workspace 8-byte aligned and >= the
+ * entry's *_workspace_bytes(h, w) (0 for sizes it refuses), else STP_E_WORKSPACE.
+ *
+ *   pred, truth : int32 label images [h][w], 0 = background; ANY label images (values need not be contiguous), not only stp_mask_label's.
+ *   label_cap   : labels lie in 0..label_cap; 0 <= label_cap <= h * w, else BADARG (stp_mask_label's output: (h * w + 1) / 2 is enough).
+ *                 A value outside 0..label_cap (a negative one too) is background in that image - it never becomes an index - and the
+ *                 pixel is counted once, in either image or both, as out of range.
+ *   arithmetic  : A_p[a], A_g[b] = the pixel counts of the labels;  I[a][b] = the pixels with pred = a and truth = b, both > 0;
+ *                 U = A_p[a] + A_g[b] - I.  The thresholds are t_k = iou_num[k] / iou_den (iou_num: a HOST pointer to T int32):
+ *                 1 <= T <= 64, 1 <= iou_den <= 1000, iou_den <= 2 * iou_num[k], iou_num[k] <= iou_den, strictly ascending, else BADARG.
+ *                 The pair (a, b) matches at t_k iff  I * iou_den > iou_num[k] * U  in int64 - the strict iou > t of the competitions'
+ *                 notebooks; t = 1 matches nothing.  As t >= 1/2 a label has at most one partner, so TP_k = the number of matching pairs:
+ *                 there is no assignment step.
+ *   the table   : row stretches of equal (pred, truth), both non-zero, found with wave ballots, make one insert each into an
+ *                 open-addressing table keyed by (a << 32) | b.  It has the smallest power of two >= 2 * h * w slots (12 bytes each)
+ *                 and at most h * w keys - every pair owns a pixel -, so the load stays <= 1/2 and every probe sequence ends.  Its clear
+ *                 and its final pass cost in proportion to the slots, not to the pairs.
+ *
+ *   stp_label_match    : out (int64, device, 8-byte aligned, T + 3 entries, all written):  out[k] = TP_k for k < T,  out[T] = the pred
+ *                        labels with A_p > 0,  out[T + 1] = the truth labels with A_g > 0,  out[T + 2] = the out-of-range pixels.
+ *                        3 launches: clear, count (areas + table), finalize (T comparisons per pair, pre-summed per workgroup).
+ *   stp_label_overlaps : the same inputs without thresholds.  triples[k] = (a, b, I) int32 for k < *count, the non-empty pairs in an
+ *                        UNSPECIFIED order (sort them); triples past *count are not written.  capacity (triples it holds) >= h * w, else
+ *                        BADARG.  area_p, area_g: int32 [label_cap + 1], all written (entry 0 is 0).  *out_of_range: int64, 8-byte
+ *                        aligned.  3 launches: clear, count, emit. */
+size_t stp_label_match_workspace_bytes(int32_t h, int32_t w);
+int stp_label_match(const int32_t* pred, const int32_t* truth, int32_t h, int32_t w, int32_t label_cap, const int32_t* iou_num, int32_t T,
+                    int32_t iou_den, int64_t* out, void* workspace, size_t workspace_bytes, void* stream);
+size_t stp_label_overlaps_workspace_bytes(int32_t h, int32_t w);
+int stp_label_overlaps(const int32_t* pred, const int32_t* truth, int32_t h, int32_t w, int32_t label_cap, int32_t* triples, int32_t* count,
+                       int64_t capacity, int32_t* area_p, int32_t* area_g, int64_t* out_of_range, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

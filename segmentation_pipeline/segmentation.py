@@ -590,6 +590,186 @@ class PipelineConfig(generic.GenericTaskConfig):
         table = {t: float(v) for t, v in zip(thresholds, scores)}
         return thresholds[int(np.argmax(scores))], table
 
+    # ---------------------------------------------------------------- object-level scores on the device (csrc/object_match.hip)
+    OBJECT_METRICS = ("f2", "ap")
+    IOU_DEN = 1000                    # IoU thresholds are exact fractions n / 1000: decimals of up to three places
+
+    @staticmethod
+    def object_score(metric, TP, n_pred, n_truth):
+        """float64 per-object scores from integer counters (arrays broadcast): TP matched pairs, ``n_pred`` predicted objects, ``n_truth``
+        objects of the target; FP = n_pred - TP, FN = n_truth - TP.  ``"f2"`` 5TP / (5TP + 4FN + FP) (Airbus ship detection), ``"ap"``
+        TP / (TP + FP + FN) (DSB-2018); 1 where n_pred = n_truth = 0, as ``sweep_score``."""
+        if metric not in PipelineConfig.OBJECT_METRICS:
+            raise ValueError("metric %r: one of %s" % (metric, ", ".join(PipelineConfig.OBJECT_METRICS)))
+        TP, P, G = (np.asarray(a, np.float64) for a in (TP, n_pred, n_truth))
+        FP, FN = P - TP, G - TP
+        num, den = (5 * TP, 5 * TP + 4 * FN + FP) if metric == "f2" else (TP, TP + FP + FN)
+        empty = (P == 0) & (G == 0)
+        return np.where(empty, 1.0, num / np.where(empty, 1.0, den))
+
+    @classmethod
+    def _iou_fractions(cls, iou_thresholds):
+        """-> (numerators, the thresholds as n / 1000): each value a decimal of at most three places in [0.5, 1], strictly ascending, 1 to 64
+        of them; default 0.5, 0.55, ..., 0.95."""
+        if iou_thresholds is None:
+            nums = list(range(500, 1000, 50))
+        else:
+            nums = []
+            for t in iou_thresholds:
+                t = float(t)
+                n = int(round(t * cls.IOU_DEN)) if np.isfinite(t) else -1
+                if n < 0 or abs(t * cls.IOU_DEN - n) > 1e-6:
+                    raise ValueError("iou_thresholds are decimals of at most three places: got %r" % (t,))
+                nums.append(n)
+        if not 1 <= len(nums) <= 64:
+            raise ValueError("1 to 64 iou_thresholds: got %d" % len(nums))
+        if any(2 * n < cls.IOU_DEN or n > cls.IOU_DEN for n in nums):
+            raise ValueError("iou_thresholds lie in [0.5, 1] (below 0.5 an object could have two partners): got %r" % (list(iou_thresholds),))
+        if any(b <= a for a, b in zip(nums, nums[1:])):
+            raise ValueError("iou_thresholds must be strictly ascending")
+        return nums, [n / cls.IOU_DEN for n in nums]
+
+    def _object_args(self, cells, opening, closing, channel, area_threshold, metric, iou_thresholds, truth):
+        """The argument checks of the object-score methods, all before a model is loaded -> (mask mode, numerators, thresholds)."""
+        if metric not in self.OBJECT_METRICS:
+            raise ValueError("metric %r: one of %s" % (metric, ", ".join(self.OBJECT_METRICS)))
+        if truth not in ("mask", "labels"):
+            raise ValueError("truth %r: 'mask' (objects = the 8-connected components of y != 0) or 'labels' (y[..., 0] numbers them)" % (truth,))
+        nums, ts = self._iou_fractions(iou_thresholds)
+        mode = 0
+        for threshold, min_size in cells:
+            mode = self._mask_mode(threshold, opening, closing, channel, min_size, area_threshold)
+        return mode, nums, ts
+
+    @staticmethod
+    def _truth_labels(it, truth, channel, h, w, dev):
+        """The item's ground truth as an int32 device label image [h, w] and the largest value it may hold."""
+        import torch
+        y = np.asarray(it.y)
+        if truth == "labels":
+            plane = y if y.ndim == 2 else y[..., 0]
+            if plane.shape != (h, w):
+                raise ValueError("item %r: a %s label image for a %d x %d image" % (it.id, plane.shape, h, w))
+            if plane.dtype.kind not in "iub" or (plane.size and (int(plane.min()) < 0 or int(plane.max()) > h * w)):
+                raise ValueError("item %r: truth='labels' takes integer object numbers 0..h * w (0: background)" % (it.id,))
+            return torch.from_numpy(np.ascontiguousarray(plane, dtype=np.int32)).to(dev), h * w
+        plane = y if y.ndim == 2 else y[:, :, channel if y.shape[2] > 1 else 0]
+        if plane.shape != (h, w):
+            raise ValueError("item %r: a %s mask for a %d x %d image" % (it.id, plane.shape, h, w))
+        mask = torch.from_numpy(np.ascontiguousarray(plane != 0).view(np.uint8)).to(dev)
+        return PipelineConfig._device_labels(mask)[0], (h * w + 1) // 2
+
+    def _object_counts(self, ds, fold, stage, negatives, ttflips, cells, mode, opening, closing, channel, area_threshold, nums, truth):
+        """-> (ids, int64 [images, cells, T + 3]): per validation item of ``fold`` the network runs once and the truth is labelled once;
+        per cell (threshold, min_size) the mask of ``predict_masks_ex``, its 8-connected labels and stp_label_match.  The counters stay
+        on the device until the one copy at the end."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        folds = self.kfold(ds, range(0, len(ds)))
+        indexes = [int(i) for i in folds.sampledIndexes(fold, False, negatives)]
+        if not indexes:
+            raise ValueError("fold %r has no validation items" % (fold,))
+        m = self.load_model(fold, stage)
+        dev, B, T = m.impl.device, m.impl.batch, len(nums)
+        counts = torch.empty((len(indexes), len(cells), T + 3), dtype=torch.int64, device=dev)
+        ids = []
+        for s in range(0, len(indexes), B):
+            items = [ds[i] for i in indexes[s:s + B]]
+            for j, (it, probs) in enumerate(zip(items, self._predict_maps_device([m], ttflips, items)[0])):
+                h, w = int(probs.shape[0]), int(probs.shape[1])
+                ids.append(it.id)
+                target, cap = self._truth_labels(it, truth, channel, h, w, dev)
+                ws = torch.empty(ops.label_match_workspace_bytes(h, w), dtype=torch.uint8, device=dev)
+                for c, (threshold, min_size) in enumerate(cells):
+                    mask = self._device_mask(probs, mode, float(threshold), int(opening), int(closing), int(channel), int(min_size),
+                                             int(area_threshold))
+                    ops.label_match(self._device_labels(mask)[0], target, h, w, cap, nums, self.IOU_DEN, counts[s + j, c], ws)
+        return ids, counts.cpu().numpy()          # the only copy back: T + 3 integers per image and cell
+
+    def score_objects(self, ds, fold, stage=-1, negatives="real", ttflips=None, threshold=0.5, opening=0, closing=0, channel=0, min_size=0,
+                      area_threshold=0, metric="f2", iou_thresholds=None, truth="mask"):
+        """The per-object competition score of ``predict_masks_ex``'s masks on the validation items of ``fold`` (chosen as ``find_threshold``
+        chooses them).  A predicted object - an 8-connected component of the mask, as ``multi_rle_encode`` splits it - is a true positive
+        at t when its IoU with an object of the item's mask exceeds t; ``iou_thresholds`` default to 0.5, 0.55, ..., 0.95 (decimals of at
+        most three places in [0.5, 1], strictly ascending, compared exactly as n / 1000).  ``metric``: ``"f2"`` (Airbus ship detection)
+        or ``"ap"`` (DSB-2018), see ``object_score``.  ``truth="mask"``: the target's objects are the 8-connected components of ``y !=
+        0``; ``"labels"``: ``y[..., 0]`` numbers them (integers 0..h * w), so touching objects stay separate.  Per image, all on the
+        device: the finished map at the image's own size, the mask (threshold, opening, closing, ``min_size``, ``area_threshold`` - the
+        launches of ``predict_masks_ex``), stp_mask_label, the labelled target, stp_label_match; only T + 3 integers per image come
+        back, in one copy.  Returns ``{"score": mean over images of the mean over t, "by_iou": {t: mean over images}, "images": [(id,
+        score)], "counts": int64 [images, T + 3] = (TP per t, predicted objects, target objects, out-of-range pixels)}``."""
+        cells = [(threshold, min_size)]
+        mode, nums, ts = self._object_args(cells, opening, closing, channel, area_threshold, metric, iou_thresholds, truth)
+        ids, counts = self._object_counts(ds, fold, stage, negatives, ttflips, cells, mode, opening, closing, channel, area_threshold, nums,
+                                          truth)
+        counts = counts[:, 0]
+        T = len(nums)
+        per = self.object_score(metric, counts[:, :T], counts[:, T:T + 1], counts[:, T + 1:T + 2])          # [images, T]
+        images = per.mean(axis=1)
+        return {"score": float(images.mean()), "by_iou": {t: float(v) for t, v in zip(ts, per.mean(axis=0))},
+                "images": [(i, float(v)) for i, v in zip(ids, images)], "counts": counts}
+
+    def find_object_threshold(self, ds, fold, stage=-1, negatives="real", ttflips=None, thresholds=None, min_sizes=(0,), opening=0, closing=0,
+                              channel=0, area_threshold=0, metric="f2", iou_thresholds=None, truth="mask"):
+        """``find_threshold`` for the score the masks are judged on: the cell of the grid ``thresholds`` x ``min_sizes`` - the two
+        parameters ``predict_masks_ex`` takes; ``thresholds`` default to d / 20 for d = 1..19 - whose ``score_objects`` is best.  Per
+        image the network runs once and the target is labelled once; per cell: threshold (+ opening / closing), area filter, labels,
+        stp_label_match.  All counters ([images, cells, T + 3] int64) stay on the device and come back in one copy.  A softmax head
+        takes ``channel`` and no ``thresholds``: only ``min_sizes`` are swept.  Returns ``((best_threshold, best_min_size), {(threshold,
+        min_size): score})``; the first cell in thresholds-major order wins a tie."""
+        if self._softmax_head():
+            if thresholds is not None:
+                raise ValueError("a softmax head has one label per pixel: the mask of `channel` is argmax == channel and takes no thresholds")
+            thresholds = [0.5]
+        else:
+            thresholds = [d / 20 for d in range(1, 20)] if thresholds is None else [float(t) for t in thresholds]
+            t32 = np.asarray(thresholds, np.float32)
+            if not 1 <= len(thresholds) <= 64:
+                raise ValueError("1 to 64 thresholds in one sweep: got %d" % len(thresholds))
+            if not np.isfinite(t32).all() or not (np.diff(t32) > 0).all():
+                raise ValueError("thresholds must be finite and strictly ascending (as float32)")
+        min_sizes = list(min_sizes)
+        if not 1 <= len(min_sizes) <= 64:
+            raise ValueError("1 to 64 min_sizes in one sweep: got %d" % len(min_sizes))
+        cells = [(t, m) for t in thresholds for m in min_sizes]
+        mode, nums, ts = self._object_args(cells, opening, closing, channel, area_threshold, metric, iou_thresholds, truth)
+        if any(b <= a for a, b in zip(min_sizes, min_sizes[1:])):
+            raise ValueError("min_sizes must be strictly ascending")
+        _, counts = self._object_counts(ds, fold, stage, negatives, ttflips, cells, mode, opening, closing, channel, area_threshold, nums,
+                                        truth)
+        T = len(nums)
+        per = self.object_score(metric, counts[:, :, :T], counts[:, :, T:T + 1], counts[:, :, T + 1:T + 2])   # [images, cells, T]
+        scores = [float(np.ascontiguousarray(per[:, c]).mean(axis=1).mean()) for c in range(len(cells))]      # score_objects' own sums
+        table = dict(zip(cells, scores))
+        return cells[int(np.argmax(scores))], table
+
+    @staticmethod
+    def object_overlaps(pred_labels, truth_labels):
+        """The overlap table of two integer label images [h, w] (numpy, 0 = background, values 0..h * w) for custom object metrics ->
+        ``(pairs, area_pred, area_truth)``: ``pairs`` int32 [k, 3] = (a, b, pixels with pred = a and truth = b) for every pair that shares
+        a pixel, sorted by (a, b); ``area_*`` int32 [max label + 1] = the labels' pixel counts.  stp_label_overlaps on the device."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        p, g = np.asarray(pred_labels), np.asarray(truth_labels)
+        if p.ndim != 2 or p.shape != g.shape or p.size == 0 or p.dtype.kind not in "iub" or g.dtype.kind not in "iub":
+            raise ValueError("object_overlaps takes two non-empty integer label images of one shape [h, w]")
+        h, w = p.shape
+        cap = int(max(p.max(), g.max()))
+        if int(min(p.min(), g.min())) < 0 or cap > h * w:
+            raise ValueError("labels are object numbers 0..h * w (0: background)")
+        dev = "cuda"
+        pd, gd = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev) for a in (p, g))
+        triples = torch.empty((h * w, 3), dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        areas = torch.empty((2, cap + 1), dtype=torch.int32, device=dev)
+        outside = torch.empty(1, dtype=torch.int64, device=dev)
+        ws = torch.empty(ops.label_overlaps_workspace_bytes(h, w), dtype=torch.uint8, device=dev)
+        ops.label_overlaps(pd, gd, h, w, cap, triples, count, areas[0], areas[1], outside, ws)
+        pairs = triples[:int(count.item())].cpu().numpy()
+        pairs = pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))]          # the device's order is unspecified: sorted by (a, b)
+        areas = areas.cpu().numpy()
+        return pairs, areas[0], areas[1]
+
 
 class PredictedMap(object):
     """What callbacks receive in place of imgaug's SegmentationMapOnImage: ``.arr`` is the HxWxC array."""

@@ -226,6 +226,10 @@ SIGNATURES = {
     "stp_mask_area_filter": (i32, [vp, vp, i32, i32, i32, i32, i64, vp, sz, vp]),
     "stp_label_rle_workspace_bytes": (sz, [i32, i32]),
     "stp_label_rle": (i32, [vp, i32, i32, vp, vp, i64, vp, sz, vp]),
+    "stp_label_match_workspace_bytes": (sz, [i32, i32]),
+    "stp_label_match": (i32, [vp, vp, i32, i32, i32, C.POINTER(i32), i32, i32, vp, vp, sz, vp]),
+    "stp_label_overlaps_workspace_bytes": (sz, [i32, i32]),
+    "stp_label_overlaps": (i32, [vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, sz, vp]),
 }
 
 _libs = {}          # storage format ("bf16" | "fp16") -> loaded library

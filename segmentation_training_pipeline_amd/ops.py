@@ -472,3 +472,39 @@ def label_rle(labels, h, w, runs, count, workspace):
         raise ValueError("label_rle: an int32 image of h x w, int32 runs and count")
     _lib.call("stp_label_rle", ptr(_dev(labels)), h, w, ptr(_dev(runs)), ptr(_dev(count)), runs.numel() // 3, ptr(_dev(workspace)),
               _nbytes(workspace), stream())
+
+
+# object-level matching on the device (csrc/object_match.hip): two int32 label images [h, w] -> true positives per IoU threshold, overlaps
+def label_match_workspace_bytes(h, w):
+    return int(_lib.load().stp_label_match_workspace_bytes(h, w))
+
+
+def label_match(pred, truth, h, w, label_cap, iou_num, iou_den, out, workspace):
+    """``out`` int64 [T + 3] = (TP_k for the T thresholds ``iou_num[k] / iou_den`` - a host sequence of integers -, pred labels, truth
+    labels, out-of-range pixels) of the int32 label images ``pred`` and ``truth`` [h, w] with values 0..label_cap."""
+    if pred.numel() < h * w or truth.numel() < h * w or pred.dtype != torch.int32 or truth.dtype != torch.int32:
+        raise ValueError("label_match: two int32 label images of h x w")
+    T = len(iou_num)
+    if out.dtype != torch.int64 or out.numel() < T + 3:
+        raise ValueError("label_match: int64 out [T + 3]")
+    num = (C.c_int32 * max(T, 1))(*[int(v) for v in iou_num])
+    _lib.call("stp_label_match", ptr(_dev(pred)), ptr(_dev(truth)), h, w, int(label_cap), num, T, int(iou_den), ptr(_dev(out)),
+              ptr(_dev(workspace)), _nbytes(workspace), stream())
+
+
+def label_overlaps_workspace_bytes(h, w):
+    return int(_lib.load().stp_label_overlaps_workspace_bytes(h, w))
+
+
+def label_overlaps(pred, truth, h, w, label_cap, triples, count, area_p, area_g, out_of_range, workspace):
+    """``triples`` int32 [capacity, 3] = (a, b, pixels with pred = a and truth = b) of the non-empty pairs in no particular order, ``count``
+    int32 [1]; ``area_p`` / ``area_g`` int32 [label_cap + 1] = the labels' pixel counts; ``out_of_range`` int64 [1]."""
+    if pred.numel() < h * w or truth.numel() < h * w or pred.dtype != torch.int32 or truth.dtype != torch.int32:
+        raise ValueError("label_overlaps: two int32 label images of h x w")
+    if (triples.dtype != torch.int32 or count.dtype != torch.int32 or count.numel() < 1 or area_p.dtype != torch.int32
+            or area_g.dtype != torch.int32 or min(area_p.numel(), area_g.numel()) < label_cap + 1 or out_of_range.dtype != torch.int64
+            or out_of_range.numel() < 1):
+        raise ValueError("label_overlaps: int32 triples and count, int32 areas [label_cap + 1], an int64 out-of-range count")
+    _lib.call("stp_label_overlaps", ptr(_dev(pred)), ptr(_dev(truth)), h, w, int(label_cap), ptr(_dev(triples)), ptr(_dev(count)),
+              triples.numel() // 3, ptr(_dev(area_p)), ptr(_dev(area_g)), ptr(_dev(out_of_range)), ptr(_dev(workspace)), _nbytes(workspace),
+              stream())
