@@ -979,6 +979,53 @@ int stp_label_overlaps(const int32_t* pred, const int32_t* truth, int32_t h, int
                        int64_t capacity, int32_t* area_p, int32_t* area_g, int64_t* out_of_range, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Splitting touching objects on the device (csrc/split.hip): a component of ONE uint8 mask [h][w] is cut at its necks - the cores of the
+ * distance transform are numbered and grown back.  uint8 and int32 only (both builds export the same code); exact integer work, equal
+ * to the host statement (tests/_split_reference.py) bit for bit and byte-identical from run to run; no atomics, no workgroup waits for
+ * another, and within a launch no workgroup reads what another one writes.  The rules of the component entries hold: STP_E_BADARG
+ * before any launch for a NULL pointer, h or w < 1 and what is listed below; never a synchronisation or an allocation; workspace
+ * 8-byte aligned and >= the entry's *_workspace_bytes(h, w) (0 for sizes it refuses), else STP_E_WORKSPACE.  Sizes: h, w <= 32767 and
+ * h * w < 2^31, else BADARG - D2 <= 2 * 32766^2 = 2147221512 then stays below 2147483647 and every product is an int32.
+ *
+ * The arithmetic.  M = the mask (any non-zero byte is foreground), c2 >= 0 an integer, the squared core distance (a radius r: c2 =
+ * floor(r * r); as D2 is an integer, D2 > r^2 is D2 > c2).
+ *   1. D2[p] = 0 off the foreground, else min over the background pixels q of the image of |p - q|^2 (int32); what lies outside the image
+ *      is not background.  With at least one zero in M this is the exact integer squared distance of scipy.ndimage.distance_transform_edt.
+ *      With no zero pixel anywhere every D2 is 2147483647.
+ *   2. Cores C = {D2 > c2}, numbered 1..nc by stp_mask_label with connectivity 2.
+ *   3. Growth: a foreground pixel outside C takes the label of the core that reaches it first through foreground pixels over the
+ *      8-neighbourhood, the smaller label winning a tie: (length of a shortest 8-path inside M, label) is the lexicographically smallest
+ *      pair over all cores; equally, the synchronous iteration "every unlabelled foreground pixel with a labelled neighbour takes the
+ *      smallest neighbouring label" until nothing changes.  Every resulting object is 8-connected.
+ *   4. The foreground pixels still at 0 (components without a core) are numbered 1..nr by stp_mask_label, connectivity 2, and take
+ *      nc + that number; nc + nr objects in all.  c2 = 0 makes the whole mask core: the result is stp_mask_label(M, connectivity 2).
+ *
+ *   stp_mask_edt        : d2[h][w] (int32, all written) = D2 of img.  2 launches: rows (one wave per row, the nearest zero from 64-lane
+ *                         ballots, a uint16 distance per pixel in the workspace), columns (a workgroup holds 32 columns of those in LDS
+ *                         - h <= 1024, else it reads them from global memory - and each pixel looks at the rows dy = 1, 2, ... above
+ *                         and below while dy * dy < its best).
+ *   stp_edt_threshold   : out[h][w] (uint8 {0, 1}) = d2 > c2.  BADARG: c2 < 0.  One d2 serves many c2.
+ *   stp_label_grow      : labels[h][w] (int32, all written) = seeds[h][w] (int32, 0 = none, else 1..h * w; ANY such image, not only
+ *                         cores; a seed off the foreground is dropped) grown through mask by stp_label_grow_rounds() = 32 synchronous
+ *                         rounds of rule 3, fewer if the state stops changing (the rounds after that do nothing).  *changed (int32,
+ *                         device) = 1 if the last round still changed a pixel - call again with seeds = labels (seeds == labels is
+ *                         allowed) until it is 0 -, else 0.  1 + 32 launches that ping-pong between labels and the workspace; a round
+ *                         reads the "changed" word the round before it wrote.
+ *   stp_label_unclaimed : out[h][w] (uint8 {0, 1}) = mask != 0 and labels == 0.
+ *   stp_label_merge     : labels[i] = rest[i] + *nc where rest[i] != 0, else unchanged; *total = *nc + *nr.  nc, nr, total: int32 on the
+ *                         device (read there: no host round trip); total is neither nc nor nr and rest is not labels, else BADARG. */
+size_t stp_mask_edt_workspace_bytes(int32_t h, int32_t w);
+int stp_mask_edt(const uint8_t* img, int32_t h, int32_t w, int32_t* d2, void* workspace, size_t workspace_bytes, void* stream);
+int stp_edt_threshold(const int32_t* d2, int32_t h, int32_t w, int32_t c2, uint8_t* out, void* stream);
+size_t stp_label_grow_workspace_bytes(int32_t h, int32_t w);
+int32_t stp_label_grow_rounds(void);
+int stp_label_grow(const uint8_t* mask, const int32_t* seeds, int32_t h, int32_t w, int32_t* labels, int32_t* changed, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int stp_label_unclaimed(const uint8_t* mask, const int32_t* labels, int32_t h, int32_t w, uint8_t* out, void* stream);
+int stp_label_merge(const int32_t* rest, const int32_t* nc, const int32_t* nr, int32_t h, int32_t w, int32_t* labels, int32_t* total,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

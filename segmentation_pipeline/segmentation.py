@@ -466,19 +466,23 @@ class PipelineConfig(generic.GenericTaskConfig):
         return [" ".join(map(str, runs[cuts[k]:cuts[k + 1], 1:].reshape(-1).tolist())) for k in range(count)]
 
     @classmethod
-    def _device_multi_rle(cls, mask):
-        """impl.rle.multi_rle_encode of a device mask: stp_mask_label (connectivity 2), stp_label_rle, then the two counts and the first
-        ``runs`` triples come back and are grouped by label on the host."""
+    def _device_label_codes(cls, labels, count):
+        """One run-length string per value 1..count of a device label image: stp_label_rle, then the two counts and the first ``runs``
+        triples come back and are grouped by label on the host."""
         from segmentation_training_pipeline_amd import ops
         import torch
-        h, w = (int(v) for v in mask.shape)
-        labels, count = cls._device_labels(mask)
-        runs = torch.empty((h * w, 3), dtype=torch.int32, device=mask.device)
-        nruns = torch.empty(1, dtype=torch.int32, device=mask.device)
-        ws = torch.empty(ops.label_rle_workspace_bytes(h, w), dtype=torch.uint8, device=mask.device)
+        h, w = (int(v) for v in labels.shape)
+        runs = torch.empty((h * w, 3), dtype=torch.int32, device=labels.device)
+        nruns = torch.empty(1, dtype=torch.int32, device=labels.device)
+        ws = torch.empty(ops.label_rle_workspace_bytes(h, w), dtype=torch.uint8, device=labels.device)
         ops.label_rle(labels, h, w, runs, nruns, ws)
         n, k = int(count.item()), int(nruns.item())
         return cls._group_runs(runs[:k].cpu().numpy(), n)
+
+    @classmethod
+    def _device_multi_rle(cls, mask):
+        """impl.rle.multi_rle_encode of a device mask: stp_mask_label (connectivity 2), then ``_device_label_codes``."""
+        return cls._device_label_codes(*cls._device_labels(mask))
 
     def predict_masks(self, spath, fold=0, stage=0, limit=-1, ttflips=False, threshold=0.5, opening=0, closing=0, channel=0, rle=True):
         """README.md:498-525 without the host: a generator of ``(file_name, rle_string)`` - or, ``rle=False``, ``(file_name, uint8 h x w
@@ -517,17 +521,24 @@ class PipelineConfig(generic.GenericTaskConfig):
         """README.md:498-525 in one call: ``predict_masks_ex`` written as a CSV with the header ``columns``; the image column holds the file
         name up to its first ``.``.  ``components=True``: one row per object, the image name repeated; an image without objects gets
         one row with an empty code.  Returns the number of rows."""
-        import csv
         if len(columns) != 2:
             raise ValueError("columns names the image column and the run-length column")
         rows = self.predict_masks_ex(spath, fold, stage, limit, ttflips, threshold, opening, closing, channel, True, min_size, area_threshold,
                                      components)
+        return self._write_csv(csv_path, columns, rows, components)
+
+    @staticmethod
+    def _write_csv(csv_path, columns, rows, per_object):
+        """The CSV of ``predict_to_csv`` / ``predict_instances_to_csv``: the header ``columns``, then per ``(name, code)`` of ``rows`` one row
+        - ``per_object``: one row per string of the list ``code``, and one row with an empty code for an empty list.  Returns the number of
+        rows."""
+        import csv
         n = 0
         with open(csv_path, "w", newline="") as f:
             out = csv.writer(f, lineterminator="\n")
             out.writerow(list(columns))
             for name, code in rows:
-                for c in ((code or [""]) if components else [code]):
+                for c in ((code or [""]) if per_object else [code]):
                     out.writerow([name[0:name.index(".")] if "." in name else name, c])
                     n += 1
         return n
@@ -637,7 +648,7 @@ class PipelineConfig(generic.GenericTaskConfig):
             raise ValueError("truth %r: 'mask' (objects = the 8-connected components of y != 0) or 'labels' (y[..., 0] numbers them)" % (truth,))
         nums, ts = self._iou_fractions(iou_thresholds)
         mode = 0
-        for threshold, min_size in cells:
+        for threshold, min_size in (c[:2] for c in cells):
             mode = self._mask_mode(threshold, opening, closing, channel, min_size, area_threshold)
         return mode, nums, ts
 
@@ -661,8 +672,10 @@ class PipelineConfig(generic.GenericTaskConfig):
 
     def _object_counts(self, ds, fold, stage, negatives, ttflips, cells, mode, opening, closing, channel, area_threshold, nums, truth):
         """-> (ids, int64 [images, cells, T + 3]): per validation item of ``fold`` the network runs once and the truth is labelled once;
-        per cell (threshold, min_size) the mask of ``predict_masks_ex``, its 8-connected labels and stp_label_match.  The counters stay
-        on the device until the one copy at the end."""
+        per cell (threshold, min_size) the mask of ``predict_masks_ex``, its 8-connected labels and stp_label_match.  A cell (threshold,
+        min_size, c2) scores the split objects instead (``_device_split``; c2 the squared core distance): consecutive cells of one
+        (threshold, min_size) share the mask and its stp_mask_edt, so a cell costs the threshold of D2, label, grow and match.  The
+        counters stay on the device until the one copy at the end."""
         from segmentation_training_pipeline_amd import ops
         import torch
         folds = self.kfold(ds, range(0, len(ds)))
@@ -680,10 +693,19 @@ class PipelineConfig(generic.GenericTaskConfig):
                 ids.append(it.id)
                 target, cap = self._truth_labels(it, truth, channel, h, w, dev)
                 ws = torch.empty(ops.label_match_workspace_bytes(h, w), dtype=torch.uint8, device=dev)
-                for c, (threshold, min_size) in enumerate(cells):
-                    mask = self._device_mask(probs, mode, float(threshold), int(opening), int(closing), int(channel), int(min_size),
-                                             int(area_threshold))
-                    ops.label_match(self._device_labels(mask)[0], target, h, w, cap, nums, self.IOU_DEN, counts[s + j, c], ws)
+                shared = (None, None, None)                  # ((threshold, min_size), its mask, its distance transform)
+                for c, (threshold, min_size, *c2) in enumerate(cells):
+                    if not c2:
+                        mask = self._device_mask(probs, mode, float(threshold), int(opening), int(closing), int(channel), int(min_size),
+                                                 int(area_threshold))
+                        ops.label_match(self._device_labels(mask)[0], target, h, w, cap, nums, self.IOU_DEN, counts[s + j, c], ws)
+                        continue
+                    if shared[0] != (threshold, min_size):
+                        mask = self._device_mask(probs, mode, float(threshold), int(opening), int(closing), int(channel), int(min_size),
+                                                 int(area_threshold))
+                        shared = ((threshold, min_size), mask, self._device_edt(mask))
+                    labels, _ = self._device_split(shared[1], c2[0], shared[2])
+                    ops.label_match(labels, target, h, w, h * w, nums, self.IOU_DEN, counts[s + j, c], ws)
         return ids, counts.cpu().numpy()          # the only copy back: T + 3 integers per image and cell
 
     def score_objects(self, ds, fold, stage=-1, negatives="real", ttflips=None, threshold=0.5, opening=0, closing=0, channel=0, min_size=0,
@@ -769,6 +791,148 @@ class PipelineConfig(generic.GenericTaskConfig):
         pairs = pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))]          # the device's order is unspecified: sorted by (a, b)
         areas = areas.cpu().numpy()
         return pairs, areas[0], areas[1]
+
+    # ---------------------------------------------------------------- touching objects split on the device (csrc/split.hip)
+    MAX_SPLIT = 1024
+
+    @classmethod
+    def _split_c2(cls, split):
+        """The squared core distance floor(r * r) of the public radius ``split``: a real, finite number in 0..1024, not a bool."""
+        if isinstance(split, (bool, np.bool_)) or not isinstance(split, (int, float, np.integer, np.floating)):
+            raise ValueError("split is the radius of the cores, a number in 0..%d (0: off): got %r" % (cls.MAX_SPLIT, split))
+        r = float(split)
+        if not np.isfinite(r) or not 0 <= r <= cls.MAX_SPLIT:
+            raise ValueError("split is the radius of the cores, a finite number in 0..%d (0: off): got %r" % (cls.MAX_SPLIT, split))
+        return int(np.floor(r * r))
+
+    @staticmethod
+    def _device_edt(mask):
+        """-> int32 device image [h, w]: stp_mask_edt of a device mask, the exact squared distance to the nearest zero pixel."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        h, w = (int(v) for v in mask.shape)
+        d2 = torch.empty((h, w), dtype=torch.int32, device=mask.device)
+        ws = torch.empty(ops.mask_edt_workspace_bytes(h, w), dtype=torch.uint8, device=mask.device)
+        ops.mask_edt(mask, h, w, d2, ws)
+        return d2
+
+    @classmethod
+    def _device_split(cls, mask, c2, d2=None):
+        """-> (int32 device label image [h, w], device count [1]): the objects of a device mask with every component cut at its necks.
+        The cores ``d2 > c2`` (``d2``: the mask's ``_device_edt``, computed here when None) are numbered by stp_mask_label (connectivity
+        2) and grown back through the mask by stp_label_grow - a pixel takes the core that reaches it first over the 8-neighbourhood,
+        the smaller number on a tie -; the components no core reached are numbered after them (stp_label_unclaimed, stp_mask_label,
+        stp_label_merge).  The only values read on the host are stp_label_grow's "changed" words, one per call."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        h, w = (int(v) for v in mask.shape)
+        if d2 is None:
+            d2 = cls._device_edt(mask)
+        part = torch.empty((h, w), dtype=torch.uint8, device=mask.device)
+        ops.edt_threshold(d2, h, w, c2, part)
+        labels, nc = cls._device_labels(part)
+        words = torch.empty(2, dtype=torch.int32, device=mask.device)
+        ws = torch.empty(ops.label_grow_workspace_bytes(h, w), dtype=torch.uint8, device=mask.device)
+        ops.label_grow(mask, labels, h, w, labels, words[:1], ws)
+        ops.label_unclaimed(mask, labels, h, w, part)
+        rest, nr = cls._device_labels(part)
+        ops.label_merge(rest, nc, nr, h, w, labels, words[1:])
+        return labels, words[1:]
+
+    @staticmethod
+    def split_labels(mask, split):
+        """The split objects of a numpy mask [h, w] (any non-zero value is foreground) for custom code -> ``(int32 label image, count)``:
+        what ``predict_instances(rle=False, split=split)`` makes of its mask, on the device.  ``split=0``: scipy.ndimage.label with the
+        8-neighbourhood."""
+        import torch
+        c2 = PipelineConfig._split_c2(split)
+        m = np.asarray(mask)
+        if m.ndim != 2 or m.size == 0 or m.dtype.kind not in "iubf":
+            raise ValueError("split_labels takes a non-empty numeric mask [h, w]")
+        dm = torch.from_numpy(np.ascontiguousarray(m != 0).view(np.uint8)).to("cuda")
+        labels, count = PipelineConfig._device_split(dm, c2)
+        return labels.cpu().numpy(), int(count.item())
+
+    def predict_instances(self, spath, fold=0, stage=0, limit=-1, ttflips=False, threshold=0.5, opening=0, closing=0, channel=0, rle=True,
+                          min_size=0, area_threshold=0, split=0.0):
+        """``predict_masks_ex(components=True)`` with touching objects kept apart: a generator of ``(file_name, [rle_string, ...])``, one
+        string per object in label order - or, ``rle=False``, ``(file_name, int32 h x w label image)``.  Per image the launches of
+        ``predict_masks_ex`` make the mask; then every 8-connected component is cut at its necks: the pixels farther than ``split``
+        from the background (exact Euclidean distance; ``split`` a radius in pixels, 0..1024) form the cores, which are numbered in
+        scipy's order and grown back through the mask - a pixel joins the core that reaches it first over the 8-neighbourhood, the
+        smaller number on a tie -, and a component without a core stays one object, numbered after the cores.  ``split=0`` is
+        ``components=True`` bit for bit.  Unlike a larger ``opening`` this removes no pixel: the objects partition the mask."""
+        mode = self._mask_mode(threshold, opening, closing, channel, min_size, area_threshold)      # (refusals fire here, not at the first next())
+        c2 = self._split_c2(split)
+
+        def instances():
+            for items, maps in self._predict_batches(spath, fold, stage, limit, ttflips, self.PROBS, device=True):
+                for it, probs in zip(items, maps):
+                    mask = self._device_mask(probs, mode, float(threshold), int(opening), int(closing), int(channel), int(min_size),
+                                             int(area_threshold))
+                    labels, count = self._device_split(mask, c2)
+                    yield it.id, (self._device_label_codes(labels, count) if rle else labels.cpu().numpy())
+        return instances()
+
+    def predict_instances_to_csv(self, spath, csv_path, fold=0, stage=0, limit=-1, ttflips=False, threshold=0.5, opening=0, closing=0,
+                                 channel=0, columns=("image", "rle_mask"), min_size=0, area_threshold=0, split=0.0):
+        """``predict_instances`` written as ``predict_to_csv(components=True)`` writes its objects: one row per object, the image name
+        repeated; an image without objects gets one row with an empty code.  Returns the number of rows."""
+        if len(columns) != 2:
+            raise ValueError("columns names the image column and the run-length column")
+        rows = self.predict_instances(spath, fold, stage, limit, ttflips, threshold, opening, closing, channel, True, min_size, area_threshold,
+                                      split)
+        return self._write_csv(csv_path, columns, rows, True)
+
+    def score_instances(self, ds, fold, stage=-1, negatives="real", ttflips=None, threshold=0.5, opening=0, closing=0, channel=0, min_size=0,
+                        area_threshold=0, metric="f2", iou_thresholds=None, truth="mask", split=0.0):
+        """``score_objects`` of ``predict_instances``' objects: the same arguments, then ``split``; the same dict.  The target is handled
+        exactly as there (``truth="mask"`` / ``"labels"``) and is never split.  ``split=0`` gives ``score_objects``' counters."""
+        cells = [(threshold, min_size, self._split_c2(split))]
+        mode, nums, ts = self._object_args(cells, opening, closing, channel, area_threshold, metric, iou_thresholds, truth)
+        ids, counts = self._object_counts(ds, fold, stage, negatives, ttflips, cells, mode, opening, closing, channel, area_threshold, nums,
+                                          truth)
+        counts = counts[:, 0]
+        T = len(nums)
+        per = self.object_score(metric, counts[:, :T], counts[:, T:T + 1], counts[:, T + 1:T + 2])          # [images, T]
+        images = per.mean(axis=1)
+        return {"score": float(images.mean()), "by_iou": {t: float(v) for t, v in zip(ts, per.mean(axis=0))},
+                "images": [(i, float(v)) for i, v in zip(ids, images)], "counts": counts}
+
+    def find_split(self, ds, fold, stage=-1, negatives="real", ttflips=None, thresholds=None, splits=(0, 2, 4, 6), min_size=0, opening=0,
+                   closing=0, channel=0, area_threshold=0, metric="f2", iou_thresholds=None, truth="mask"):
+        """``find_object_threshold`` over the grid ``thresholds`` x ``splits`` (1 to 64 radii, strictly ascending): the cell whose
+        ``score_instances`` is best.  Per image the network runs once and the target is labelled once; per threshold the mask and its
+        distance transform are made once; per split only the threshold of the distances, the labels, the growth and stp_label_match
+        run.  A softmax head takes ``channel`` and no ``thresholds``.  Returns ``((best_threshold, best_split), {(threshold, split):
+        score})``; the first cell in thresholds-major order wins a tie."""
+        if self._softmax_head():
+            if thresholds is not None:
+                raise ValueError("a softmax head has one label per pixel: the mask of `channel` is argmax == channel and takes no thresholds")
+            thresholds = [0.5]
+        else:
+            thresholds = [d / 20 for d in range(1, 20)] if thresholds is None else [float(t) for t in thresholds]
+            t32 = np.asarray(thresholds, np.float32)
+            if not 1 <= len(thresholds) <= 64:
+                raise ValueError("1 to 64 thresholds in one sweep: got %d" % len(thresholds))
+            if not np.isfinite(t32).all() or not (np.diff(t32) > 0).all():
+                raise ValueError("thresholds must be finite and strictly ascending (as float32)")
+        splits = list(splits)
+        if not 1 <= len(splits) <= 64:
+            raise ValueError("1 to 64 splits in one sweep: got %d" % len(splits))
+        c2s = [self._split_c2(r) for r in splits]
+        if any(b <= a for a, b in zip(splits, splits[1:])):
+            raise ValueError("splits must be strictly ascending")
+        keys = [(t, r) for t in thresholds for r in splits]
+        cells = [(t, min_size, c2) for t in thresholds for c2 in c2s]
+        mode, nums, ts = self._object_args(cells, opening, closing, channel, area_threshold, metric, iou_thresholds, truth)
+        _, counts = self._object_counts(ds, fold, stage, negatives, ttflips, cells, mode, opening, closing, channel, area_threshold, nums,
+                                        truth)
+        T = len(nums)
+        per = self.object_score(metric, counts[:, :, :T], counts[:, :, T:T + 1], counts[:, :, T + 1:T + 2])   # [images, cells, T]
+        scores = [float(np.ascontiguousarray(per[:, c]).mean(axis=1).mean()) for c in range(len(cells))]      # score_instances' own sums
+        table = dict(zip(keys, scores))
+        return keys[int(np.argmax(scores))], table
 
 
 class PredictedMap(object):

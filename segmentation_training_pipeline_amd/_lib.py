@@ -230,6 +230,14 @@ SIGNATURES = {
     "stp_label_match": (i32, [vp, vp, i32, i32, i32, C.POINTER(i32), i32, i32, vp, vp, sz, vp]),
     "stp_label_overlaps_workspace_bytes": (sz, [i32, i32]),
     "stp_label_overlaps": (i32, [vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, sz, vp]),
+    "stp_mask_edt_workspace_bytes": (sz, [i32, i32]),
+    "stp_mask_edt": (i32, [vp, i32, i32, vp, vp, sz, vp]),
+    "stp_edt_threshold": (i32, [vp, i32, i32, i32, vp, vp]),
+    "stp_label_grow_workspace_bytes": (sz, [i32, i32]),
+    "stp_label_grow_rounds": (i32, []),
+    "stp_label_grow": (i32, [vp, vp, i32, i32, vp, vp, vp, sz, vp]),
+    "stp_label_unclaimed": (i32, [vp, vp, i32, i32, vp, vp]),
+    "stp_label_merge": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
 }
 
 _libs = {}          # storage format ("bf16" | "fp16") -> loaded library

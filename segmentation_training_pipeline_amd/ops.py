@@ -508,3 +508,65 @@ def label_overlaps(pred, truth, h, w, label_cap, triples, count, area_p, area_g,
     _lib.call("stp_label_overlaps", ptr(_dev(pred)), ptr(_dev(truth)), h, w, int(label_cap), ptr(_dev(triples)), ptr(_dev(count)),
               triples.numel() // 3, ptr(_dev(area_p)), ptr(_dev(area_g)), ptr(_dev(out_of_range)), ptr(_dev(workspace)), _nbytes(workspace),
               stream())
+
+
+# splitting touching objects on the device (csrc/split.hip): ONE uint8 mask [h, w] -> its squared distance transform, cores, grown labels
+def mask_edt_workspace_bytes(h, w):
+    return int(_lib.load().stp_mask_edt_workspace_bytes(h, w))
+
+
+def mask_edt(img, h, w, d2, workspace):
+    """``d2`` int32 [h, w] = the exact squared Euclidean distance of every foreground pixel of the uint8 mask ``img`` to its nearest zero
+    pixel, 0 off the foreground, 2147483647 everywhere when the mask has no zero."""
+    if img.numel() < h * w or d2.numel() < h * w or img.dtype != torch.uint8 or d2.dtype != torch.int32:
+        raise ValueError("mask_edt: a uint8 image and an int32 distance image of h x w")
+    _lib.call("stp_mask_edt", ptr(_dev(img)), h, w, ptr(_dev(d2)), ptr(_dev(workspace)), _nbytes(workspace), stream())
+
+
+def edt_threshold(d2, h, w, c2, out):
+    """``out`` uint8 [h, w] = ``d2 > c2`` (c2 an integer >= 0): the cores of ``mask_edt``'s image."""
+    if d2.numel() < h * w or out.numel() < h * w or d2.dtype != torch.int32 or out.dtype != torch.uint8:
+        raise ValueError("edt_threshold: an int32 distance image and a uint8 mask of h x w")
+    _lib.call("stp_edt_threshold", ptr(_dev(d2)), h, w, int(c2), ptr(_dev(out)), stream())
+
+
+def label_grow_workspace_bytes(h, w):
+    return int(_lib.load().stp_label_grow_workspace_bytes(h, w))
+
+
+def label_grow(mask, seeds, h, w, labels, changed, workspace):
+    """``labels`` int32 [h, w] = the int32 ``seeds`` (0: none) grown through the uint8 ``mask``: every unlabelled foreground pixel takes
+    the label that reaches it first over the 8-neighbourhood, the smaller one on a tie.  One stp_label_grow call makes a bounded number
+    of rounds and leaves in ``changed`` (int32 [1]) whether the last still changed a pixel; this wrapper calls again from ``labels``
+    until it is clear, reading the word once per call.  Returns the number of calls."""
+    if (mask.numel() < h * w or seeds.numel() < h * w or labels.numel() < h * w or mask.dtype != torch.uint8 or seeds.dtype != torch.int32
+            or labels.dtype != torch.int32 or changed.dtype != torch.int32 or changed.numel() < 1):
+        raise ValueError("label_grow: a uint8 mask, int32 seeds and labels of h x w, an int32 changed word")
+    per_call = int(_lib.load().stp_label_grow_rounds())
+    src, calls = seeds, 0
+    while True:
+        _lib.call("stp_label_grow", ptr(_dev(mask)), ptr(_dev(src)), h, w, ptr(_dev(labels)), ptr(_dev(changed)), ptr(_dev(workspace)),
+                  _nbytes(workspace), stream())
+        calls += 1
+        if int(changed[0].item()) == 0:
+            return calls
+        if calls * per_call >= h * w:          # a round that changes something labels a pixel: there are fewer than h * w of them
+            raise _lib.StpError("stp_label_grow still changes pixels after %d rounds on a %d x %d image" % (calls * per_call, h, w))
+        src = labels
+
+
+def label_unclaimed(mask, labels, h, w, out):
+    """``out`` uint8 [h, w] = the foreground pixels of ``mask`` whose int32 label is 0."""
+    if (mask.numel() < h * w or labels.numel() < h * w or out.numel() < h * w or mask.dtype != torch.uint8 or labels.dtype != torch.int32
+            or out.dtype != torch.uint8):
+        raise ValueError("label_unclaimed: a uint8 mask, int32 labels and a uint8 output of h x w")
+    _lib.call("stp_label_unclaimed", ptr(_dev(mask)), ptr(_dev(labels)), h, w, ptr(_dev(out)), stream())
+
+
+def label_merge(rest, nc, nr, h, w, labels, total):
+    """``labels[i] = rest[i] + nc`` where the int32 image ``rest`` is non-zero, ``total = nc + nr``; ``nc``, ``nr``, ``total``: int32 [1] on
+    the device (``total`` is neither of the other two)."""
+    if (rest.numel() < h * w or labels.numel() < h * w or rest.dtype != torch.int32 or labels.dtype != torch.int32
+            or any(t.dtype != torch.int32 or t.numel() < 1 for t in (nc, nr, total))):
+        raise ValueError("label_merge: two int32 label images of h x w, three int32 counts")
+    _lib.call("stp_label_merge", ptr(_dev(rest)), ptr(_dev(nc)), ptr(_dev(nr)), h, w, ptr(_dev(labels)), ptr(_dev(total)), stream())
