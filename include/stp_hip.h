@@ -677,15 +677,19 @@ size_t stp_dwconv_wgrad_workspace_bytes(int32_t C, int32_t k);
 int stp_dwconv_wgrad(const void* x, const void* dy, float* dw, int32_t N, int32_t H, int32_t W, int32_t C, int32_t k,
                      int32_t stride, int32_t pad_t, int32_t pad_l, int32_t dilation, int32_t Ho, int32_t Wo, int32_t dtype,
                      int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
-/* tf.image.resize_bilinear(align_corners=True) to any output size (BilinearUpsampling, model.py:94-100) and its gradient
- * (fixed-order gather).  Dense [N,H,W,C] tensors, any C. */
+/* tf.image.resize_bilinear(align_corners=True) to any output size, larger or smaller than the input (BilinearUpsampling,
+ * model.py:94-100) and its gradient (fixed-order gather).  Dense [N,H,W,C] tensors, any C.  Per axis, in fp32:
+ * s = float(H-1) / float(Ho-1) (0 when Ho == 1), src = float(yo) * s, y0 = floor(src), y1 = min(y0+1, H-1), f = src - y0.
+ * The forward evaluates v0 + (v1 - v0) * f along x for both rows, then along y, and rounds once to the storage dtype; the
+ * gradient is the adjoint with weights (1 - f) and f (dx = Ry^T dy Rx, + dx when accumulate), rounded once. */
 int stp_resize_bilinear_ac(const void* x, void* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo,
                            int32_t dtype, void* stream);
 int stp_resize_bilinear_ac_bwd(const void* dy, void* dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo,
                                int32_t dtype, int32_t accumulate, void* stream);
 /* Inverted dropout (model.py:461): y = mask * x / (1 - rate), mask = counter-based hash of (state[0], salt, index) - the same
  * call with dy gives the gradient; stp_counter_tick advances state[0] (int32 on the device) once per step, so a hipGraph
- * replay draws a fresh mask.  x == y allowed. */
+ * replay draws a fresh mask.  x == y allowed.  A kept element is float(x) * (1.f / (1.f - rate)), rounded once (to nearest
+ * even) to the storage dtype; rate = 0 returns x. */
 int stp_counter_tick(int32_t* state, void* stream);
 int stp_dropout(const void* x, void* y, int64_t count, float rate, const int32_t* state, uint32_t salt, int32_t dtype, void* stream);
 /* SpatialDropout2D(rate) on [N][HW][C] (segmentation_models' FPN / PSPNet `dropout`, schemas/segmentation.raml:201-203, 241-243):
