@@ -1030,6 +1030,49 @@ int stp_label_unclaimed(const uint8_t* mask, const int32_t* labels, int32_t h, i
 int stp_label_merge(const int32_t* rest, const int32_t* nc, const int32_t* nr, int32_t h, int32_t w, int32_t* labels, int32_t* total,
                     void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Per-object measurements of a label image on the device (csrc/measure.hip): area, sums of the coordinates, a fixed-point confidence and
+ * the bounding box per label, and the selection of the objects that are large and confident enough.  int32, int64 and fp32 only (both
+ * builds export the same code); after the quantisation below everything is exact integer work, equal to the host statement
+ * (tests/_measure_reference.py) bit for bit and byte-identical from run to run.  Only integer atomics (64-bit atomicAdd on the sums, int32
+ * atomicMin / atomicMax on the boxes, in LDS and in global memory); no workgroup waits for another.  The rules of the component entries
+ * hold: STP_E_BADARG before any launch for a NULL pointer, a bad size and what is listed below; never a synchronisation or an allocation;
+ * workspace 8-byte aligned and >= stp_label_select_workspace_bytes(label_cap) (0 for label_cap < 0), else STP_E_WORKSPACE.  Sizes:
+ * 1 <= h, w <= 32767 (so h * w < 2^31), else BADARG.
+ *
+ *   labels    : an int32 label image [h][w], 0 = background; ANY label image (values need not be contiguous), not only stp_mask_label's.
+ *   label_cap : labels lie in 0..label_cap; 0 <= label_cap <= h * w, else BADARG.  A value outside 0..label_cap (a negative one too) is
+ *               background - it never becomes an index - and its pixel is counted in *out_of_range (int64, 8-byte aligned).
+ *   probs     : fp32 [h][w][C] or NULL; with probs, C >= 1 and 0 <= channel < C, else BADARG; with NULL, C and channel are ignored.
+ *   q         : the fixed-point probability of a pixel, q = (int) (clamp(p, 0, 1) * 65535.0f) with p = probs[y][x][channel]: one fp32
+ *               multiply and one truncation, 0..65535, a NaN gives 0 - numpy's (np.clip(p, 0, 1).astype(np.float32) *
+ *               np.float32(65535)).astype(np.int64) with NaN set to 0 first.  q = 0 without probs.
+ *   the table : for every label k in 0..label_cap (all rows written; sums 8-byte aligned)
+ *                 sums[k]  (int64 x 4) = (area = its pixel count, the sum of its y, the sum of its x, the sum of its q)
+ *                 boxes[k] (int32 x 4) = (min y, min x, max y, max x), CLOSED; (h, w, -1, -1) for a label without a pixel.
+ *               Row 0 is all zero with that empty box.  Derived on the host in float64: cy = sum y / area, cx = sum x / area, confidence =
+ *               sum q / (65535 * area), the half-open box (min y, min x, max y + 1, max x + 1) = scipy.ndimage.find_objects' slices.
+ *   selection : label k is kept iff  area > 0,  area >= min_area  and  sum q * conf_den >= conf_num * 65535 * area  in int64 (area < 2^31:
+ *               both products stay below 2^61).  min_area >= 0, 1 <= conf_den <= 10000, 0 <= conf_num <= conf_den, else BADARG.  The kept
+ *               labels keep their order and are renumbered 1..*count.
+ *
+ *   stp_label_measure : 2 launches: clear (the table, the counter), measure.  A wave owns 64 consecutive pixels of a row; a stretch of
+ *                       equal labels contributes once - its length, y * length, the closed-form sum of its x, its sum of q from the
+ *                       wave's prefix sum, and y, first x, last x for the box.  A workgroup combines the stretches of up to 128 labels in
+ *                       LDS and adds each once to global memory; what does not fit the LDS table goes there directly.
+ *   stp_label_select  : out_labels[i] = the new number of labels[i], 0 for a label that is dropped or out of range (out_labels == labels
+ *                       is allowed: a pixel is read and written by one thread).  *count (int32, device) = the kept labels.
+ *                       out_sums[new], out_boxes[new] = the kept rows in the new numbering; row 0 as above; rows past *count are not
+ *                       written (room for label_cap + 1 rows is enough).  out_sums == sums or out_boxes == boxes: BADARG.  4 launches:
+ *                       the kept labels per block of 256, one workgroup that scans the blocks in order, the map old -> new with the
+ *                       rows' copy, the pass over the image.  workspace: the map and the block counts. */
+int stp_label_measure(const int32_t* labels, const float* probs, int32_t h, int32_t w, int32_t C, int32_t channel, int32_t label_cap,
+                      int64_t* sums, int32_t* boxes, int64_t* out_of_range, void* stream);
+size_t stp_label_select_workspace_bytes(int32_t label_cap);
+int stp_label_select(const int32_t* labels, int32_t h, int32_t w, int32_t label_cap, const int64_t* sums, const int32_t* boxes,
+                     int64_t min_area, int32_t conf_num, int32_t conf_den, int32_t* out_labels, int32_t* count, int64_t* out_sums,
+                     int32_t* out_boxes, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

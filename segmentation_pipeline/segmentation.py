@@ -934,6 +934,255 @@ class PipelineConfig(generic.GenericTaskConfig):
         table = dict(zip(keys, scores))
         return keys[int(np.argmax(scores))], table
 
+    # ---------------------------------------------------------------- per-object measurements on the device (csrc/measure.hip)
+    CONF_ONE = 65535                  # the fixed-point probability of a pixel: q = (int)(clamp(p, 0, 1) * 65535)
+    CONF_DEN = 10000                  # min_confidence is an exact fraction n / 10000: a decimal of up to four places
+    MEASURES = ("area", "confidence", "y0", "x0", "y1", "x1", "cy", "cx")
+
+    @classmethod
+    def _conf_num(cls, min_confidence, name="min_confidence"):
+        """The numerator n of ``min_confidence`` = n / 10000: a real number in [0, 1] with at most four decimal places, not a bool."""
+        t = min_confidence
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.floating)):
+            raise ValueError("%s is a decimal of at most four places in [0, 1]: got %r" % (name, t))
+        t = float(t)
+        n = int(round(t * cls.CONF_DEN)) if np.isfinite(t) else -1
+        if n < 0 or n > cls.CONF_DEN or abs(t * cls.CONF_DEN - n) > 1e-6:
+            raise ValueError("%s is a decimal of at most four places in [0, 1]: got %r" % (name, min_confidence))
+        return n
+
+    @staticmethod
+    def _min_area(min_area):
+        if isinstance(min_area, (bool, np.bool_)) or not isinstance(min_area, (int, np.integer)) or min_area < 0:
+            raise ValueError("min_area is a pixel count, an integer >= 0 (0: off): got %r" % (min_area,))
+        return int(min_area)
+
+    @staticmethod
+    def object_table(sums, boxes, count):
+        """The per-object table of stp_label_measure's integers (``sums`` int64 [rows, 4] = area, sum y, sum x, sum q; ``boxes`` int32 [rows,
+        4] = the closed box) over the objects 1..count -> a dict of numpy arrays: ``label``, ``area`` and the half-open box ``y0``, ``x0``,
+        ``y1``, ``x1`` (scipy.ndimage.find_objects' slices) as int64; the centroid ``cy``, ``cx`` and ``confidence`` = sum q / (65535 *
+        area), the object's mean probability, as float64 (NaN for a label without a pixel)."""
+        s, b = np.asarray(sums, np.int64)[1:count + 1], np.asarray(boxes, np.int64)[1:count + 1]
+        area = s[:, 0].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return {"label": np.arange(1, count + 1, dtype=np.int64), "area": s[:, 0].copy(), "y0": b[:, 0].copy(), "x0": b[:, 1].copy(),
+                    "y1": b[:, 2] + 1, "x1": b[:, 3] + 1, "cy": s[:, 1] / area, "cx": s[:, 2] / area,
+                    "confidence": s[:, 3] / (np.float64(PipelineConfig.CONF_ONE) * area)}
+
+    @staticmethod
+    def _device_measure(labels, cap, probs=None, channel=0):
+        """-> (int64 sums [cap + 1, 4], int32 boxes [cap + 1, 4], int64 out-of-range count [1]), all on the device: stp_label_measure of
+        a device label image with values 0..cap and, optionally, the float32 device map [h, w, C]."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        h, w = (int(v) for v in labels.shape)
+        sums = torch.empty((cap + 1, 4), dtype=torch.int64, device=labels.device)
+        boxes = torch.empty((cap + 1, 4), dtype=torch.int32, device=labels.device)
+        outside = torch.empty(1, dtype=torch.int64, device=labels.device)
+        ops.label_measure(labels, probs, h, w, 1 if probs is None else int(probs.shape[2]), int(channel), cap, sums, boxes, outside)
+        return sums, boxes, outside
+
+    @classmethod
+    def _device_select(cls, labels, cap, sums, boxes, min_area, num, out=None):
+        """-> (int32 device label image, device count [1], sums, boxes): stp_label_select - the objects with ``area >= min_area`` and mean
+        probability >= num / 10000, renumbered in order, and their rows.  ``out``: the buffers of an earlier call of the same shape."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        h, w = (int(v) for v in labels.shape)
+        if out is None:
+            out = (torch.empty_like(labels), torch.empty(1, dtype=torch.int32, device=labels.device), torch.empty_like(sums),
+                   torch.empty_like(boxes), torch.empty(ops.label_select_workspace_bytes(cap), dtype=torch.uint8, device=labels.device))
+        ops.label_select(labels, h, w, cap, sums, boxes, min_area, num, cls.CONF_DEN, out[0], out[1], out[2], out[3], out[4])
+        return out
+
+    @staticmethod
+    def measure_labels(labels, probs=None, channel=0):
+        """The per-object table of a numpy label image [h, w] (integers 0..h * w, 0 = background) for custom code, on the device: the
+        ``object_table`` dict over the labels 1..labels.max() - a value that does not occur has area 0 - plus ``"out_of_range"``.
+        ``probs``: a numpy map [h, w] or [h, w, C] whose ``channel`` gives the confidence; None: confidence 0."""
+        import torch
+        lab = np.asarray(labels)
+        if lab.ndim != 2 or lab.size == 0 or lab.dtype.kind not in "iub":
+            raise ValueError("measure_labels takes a non-empty integer label image [h, w]")
+        h, w = lab.shape
+        cap = int(lab.max())
+        if int(lab.min()) < 0 or cap > h * w:
+            raise ValueError("labels are object numbers 0..h * w (0: background)")
+        dp = None
+        if probs is not None:
+            p = np.asarray(probs)
+            if p.dtype.kind not in "fiub" or p.ndim not in (2, 3) or p.shape[:2] != (h, w) or (p.ndim == 3 and p.shape[2] < 1):
+                raise ValueError("probs is a numeric map [h, w] or [h, w, C] of the label image's size")
+            p = p[:, :, None] if p.ndim == 2 else p
+            if isinstance(channel, (bool, np.bool_)) or not isinstance(channel, (int, np.integer)) or not 0 <= channel < p.shape[2]:
+                raise ValueError("channel %r: the map has %d channel(s)" % (channel, p.shape[2]))
+            dp = torch.from_numpy(np.ascontiguousarray(p, dtype=np.float32)).to("cuda")
+        dl = torch.from_numpy(np.ascontiguousarray(lab, dtype=np.int32)).to("cuda")
+        sums, boxes, outside = PipelineConfig._device_measure(dl, cap, dp, int(channel) if dp is not None else 0)
+        out = PipelineConfig.object_table(sums.cpu().numpy(), boxes.cpu().numpy(), cap)
+        out["out_of_range"] = int(outside.item())
+        return out
+
+    def predict_instances_ex(self, spath, fold=0, stage=0, limit=-1, ttflips=False, threshold=0.5, opening=0, closing=0, channel=0, rle=True,
+                             min_size=0, area_threshold=0, split=0.0, min_area=0, min_confidence=0.0, measure=False):
+        """``predict_instances`` (same arguments, and exactly its launches and results when the three new keywords keep their defaults)
+        with the objects then measured and selected on the device: after the split, stp_label_measure takes every object's area, bounding
+        box, centroid sums and the sum of ``probs[..., channel]`` of the finished map at the image's own size in 1 / 65535 units;
+        stp_label_select keeps the objects with at least ``min_area`` pixels (an integer >= 0; unlike ``min_size`` it also sees the
+        fragments a split creates) whose mean probability is at least ``min_confidence`` (a decimal of at most four places in [0, 1],
+        compared exactly as n / 10000) and renumbers them in order.  Yields ``(file_name, codes_or_labels)`` or, ``measure=True``,
+        ``(file_name, codes_or_labels, table)`` with ``table`` the ``object_table`` dict of the objects that are left."""
+        mode = self._mask_mode(threshold, opening, closing, channel, min_size, area_threshold)      # (refusals fire here, not at the first next())
+        c2 = self._split_c2(split)
+        min_area, num = self._min_area(min_area), self._conf_num(min_confidence)
+        if not (min_area or num or measure):
+            return self.predict_instances(spath, fold, stage, limit, ttflips, threshold, opening, closing, channel, rle, min_size,
+                                          area_threshold, split)
+
+        def instances():
+            for items, maps in self._predict_batches(spath, fold, stage, limit, ttflips, self.PROBS, device=True):
+                for it, probs in zip(items, maps):
+                    mask = self._device_mask(probs, mode, float(threshold), int(opening), int(closing), int(channel), int(min_size),
+                                             int(area_threshold))
+                    labels, count = self._device_split(mask, c2)
+                    n = int(count.item())
+                    sums, boxes, _ = self._device_measure(labels, n, probs, int(channel))
+                    if min_area or num:                       # (the split's labels are 1..n, each with a pixel: nothing else to drop)
+                        labels, count, sums, boxes, _ = self._device_select(labels, n, sums, boxes, min_area, num)
+                        n = int(count.item())
+                    out = self._device_label_codes(labels, count) if rle else labels.cpu().numpy()
+                    if measure:
+                        yield it.id, out, self.object_table(sums[:n + 1].cpu().numpy(), boxes[:n + 1].cpu().numpy(), n)
+                    else:
+                        yield it.id, out
+        return instances()
+
+    @classmethod
+    def _measure_names(cls, columns, measures):
+        if len(columns) != 2:
+            raise ValueError("columns names the image column and the run-length column")
+        if isinstance(measures, str) or any(m not in cls.MEASURES for m in measures):
+            raise ValueError("measures is a tuple of names from %s: got %r" % (", ".join(cls.MEASURES), measures))
+        return tuple(measures)
+
+    def predict_instances_to_csv_ex(self, spath, csv_path, fold=0, stage=0, limit=-1, ttflips=False, threshold=0.5, opening=0, closing=0,
+                                    channel=0, columns=("image", "rle_mask"), min_size=0, area_threshold=0, split=0.0, min_area=0,
+                                    min_confidence=0.0, measures=()):
+        """``predict_instances_ex`` written as ``predict_instances_to_csv`` writes its objects, with the columns named in ``measures`` (a tuple
+        of names from ``"area", "confidence", "y0", "x0", "y1", "x1", "cy", "cx"``, which are also their headers) appended: integers as
+        integers, floats with ``repr``.  An image without objects gets one row whose other fields are empty.  Returns the number of rows."""
+        import csv
+        measures = self._measure_names(columns, measures)
+        rows = self.predict_instances_ex(spath, fold, stage, limit, ttflips, threshold, opening, closing, channel, True, min_size,
+                                         area_threshold, split, min_area, min_confidence, True)
+        n = 0
+        with open(csv_path, "w", newline="") as f:
+            out = csv.writer(f, lineterminator="\n")
+            out.writerow(list(columns) + list(measures))
+            for name, codes, table in rows:
+                stem = name[0:name.index(".")] if "." in name else name
+                for k, code in enumerate(codes):
+                    cells = [table[m][k] for m in measures]
+                    out.writerow([stem, code] + [repr(float(v)) if isinstance(v, np.floating) else str(int(v)) for v in cells])
+                    n += 1
+                if not codes:
+                    out.writerow([stem] + [""] * (1 + len(measures)))
+                    n += 1
+        return n
+
+    def _selected_counts(self, ds, fold, stage, negatives, ttflips, cells, mode, opening, closing, channel, area_threshold, nums, truth):
+        """``_object_counts`` for cells (threshold, min_size, c2, min_area, conf_num) -> (ids, int64 [images, cells, T + 3]).  Per validation
+        item of ``fold`` the network runs once and the truth is labelled once; consecutive cells of one (threshold, min_size, c2) share the
+        mask, its split and ONE stp_label_measure; a cell costs stp_label_select and stp_label_match (a cell that selects nothing away
+        matches the shared labels as they are).  The counters stay on the device until the one copy at the end."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        folds = self.kfold(ds, range(0, len(ds)))
+        indexes = [int(i) for i in folds.sampledIndexes(fold, False, negatives)]
+        if not indexes:
+            raise ValueError("fold %r has no validation items" % (fold,))
+        m = self.load_model(fold, stage)
+        dev, B, T = m.impl.device, m.impl.batch, len(nums)
+        counts = torch.empty((len(indexes), len(cells), T + 3), dtype=torch.int64, device=dev)
+        ids = []
+        for s in range(0, len(indexes), B):
+            items = [ds[i] for i in indexes[s:s + B]]
+            for j, (it, probs) in enumerate(zip(items, self._predict_maps_device([m], ttflips, items)[0])):
+                h, w = int(probs.shape[0]), int(probs.shape[1])
+                ids.append(it.id)
+                target, _ = self._truth_labels(it, truth, channel, h, w, dev)
+                ws = torch.empty(ops.label_match_workspace_bytes(h, w), dtype=torch.uint8, device=dev)
+                cap = h * w                                  # (the object count stays on the device: the most an image can hold)
+                shared, table, out = None, None, None        # (threshold, min_size, c2), (its labels, sums, boxes), the selection's buffers
+                for c, (threshold, min_size, c2, min_area, num) in enumerate(cells):
+                    if shared != (threshold, min_size, c2):
+                        mask = self._device_mask(probs, mode, float(threshold), int(opening), int(closing), int(channel), int(min_size),
+                                                 int(area_threshold))
+                        labels = self._device_split(mask, c2)[0] if c2 else self._device_labels(mask)[0]
+                        shared, table = (threshold, min_size, c2), None
+                    chosen = labels
+                    if min_area or num:
+                        if table is None:
+                            table = self._device_measure(labels, cap, probs, int(channel))
+                        out = self._device_select(labels, cap, table[0], table[1], min_area, num, out)
+                        chosen = out[0]
+                    ops.label_match(chosen, target, h, w, cap, nums, self.IOU_DEN, counts[s + j, c], ws)
+        return ids, counts.cpu().numpy()          # the only copy back: T + 3 integers per image and cell
+
+    def score_instances_ex(self, ds, fold, stage=-1, negatives="real", ttflips=None, threshold=0.5, opening=0, closing=0, channel=0,
+                           min_size=0, area_threshold=0, metric="f2", iou_thresholds=None, truth="mask", split=0.0, min_area=0,
+                           min_confidence=0.0):
+        """``score_instances`` of ``predict_instances_ex``' objects: the same arguments, then ``min_area`` and ``min_confidence``; the same
+        dict.  With both at 0 the counters are ``score_instances``' own."""
+        cells = [(threshold, min_size, self._split_c2(split), self._min_area(min_area), self._conf_num(min_confidence))]
+        mode, nums, ts = self._object_args(cells, opening, closing, channel, area_threshold, metric, iou_thresholds, truth)
+        ids, counts = self._selected_counts(ds, fold, stage, negatives, ttflips, cells, mode, opening, closing, channel, area_threshold, nums,
+                                            truth)
+        counts = counts[:, 0]
+        T = len(nums)
+        per = self.object_score(metric, counts[:, :T], counts[:, T:T + 1], counts[:, T + 1:T + 2])          # [images, T]
+        images = per.mean(axis=1)
+        return {"score": float(images.mean()), "by_iou": {t: float(v) for t, v in zip(ts, per.mean(axis=0))},
+                "images": [(i, float(v)) for i, v in zip(ids, images)], "counts": counts}
+
+    def find_confidence(self, ds, fold, stage=-1, negatives="real", ttflips=None, thresholds=None, confidences=(0.0, 0.5, 0.6, 0.7, 0.8),
+                        split=0.0, min_size=0, min_area=0, opening=0, closing=0, channel=0, area_threshold=0, metric="f2",
+                        iou_thresholds=None, truth="mask"):
+        """``find_split`` over the grid ``thresholds`` x ``confidences`` (1 to 64 decimals of at most four places in [0, 1], strictly
+        ascending): the cell whose ``score_instances_ex`` is best.  Per image the network runs once and the target is labelled once; per
+        threshold the mask, its split and one stp_label_measure run once; per confidence only stp_label_select and stp_label_match run.
+        A softmax head takes ``channel`` and no ``thresholds``.  Returns ``((best_threshold, best_confidence), {(threshold, confidence):
+        score})``; the first cell in thresholds-major order wins a tie."""
+        if self._softmax_head():
+            if thresholds is not None:
+                raise ValueError("a softmax head has one label per pixel: the mask of `channel` is argmax == channel and takes no thresholds")
+            thresholds = [0.5]
+        else:
+            thresholds = [d / 20 for d in range(1, 20)] if thresholds is None else [float(t) for t in thresholds]
+            t32 = np.asarray(thresholds, np.float32)
+            if not 1 <= len(thresholds) <= 64:
+                raise ValueError("1 to 64 thresholds in one sweep: got %d" % len(thresholds))
+            if not np.isfinite(t32).all() or not (np.diff(t32) > 0).all():
+                raise ValueError("thresholds must be finite and strictly ascending (as float32)")
+        confidences = list(confidences)
+        if not 1 <= len(confidences) <= 64:
+            raise ValueError("1 to 64 confidences in one sweep: got %d" % len(confidences))
+        conf_nums = [self._conf_num(v, "confidences") for v in confidences]
+        if any(b <= a for a, b in zip(conf_nums, conf_nums[1:])):
+            raise ValueError("confidences must be strictly ascending")
+        c2, min_area = self._split_c2(split), self._min_area(min_area)
+        keys = [(t, v) for t in thresholds for v in confidences]
+        cells = [(t, min_size, c2, min_area, n) for t in thresholds for n in conf_nums]
+        mode, nums, ts = self._object_args(cells, opening, closing, channel, area_threshold, metric, iou_thresholds, truth)
+        _, counts = self._selected_counts(ds, fold, stage, negatives, ttflips, cells, mode, opening, closing, channel, area_threshold, nums,
+                                          truth)
+        T = len(nums)
+        per = self.object_score(metric, counts[:, :, :T], counts[:, :, T:T + 1], counts[:, :, T + 1:T + 2])   # [images, cells, T]
+        scores = [float(np.ascontiguousarray(per[:, c]).mean(axis=1).mean()) for c in range(len(cells))]      # score_instances_ex' own sums
+        table = dict(zip(keys, scores))
+        return keys[int(np.argmax(scores))], table
+
 
 class PredictedMap(object):
     """What callbacks receive in place of imgaug's SegmentationMapOnImage: ``.arr`` is the HxWxC array."""

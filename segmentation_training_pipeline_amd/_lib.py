@@ -238,6 +238,9 @@ SIGNATURES = {
     "stp_label_grow": (i32, [vp, vp, i32, i32, vp, vp, vp, sz, vp]),
     "stp_label_unclaimed": (i32, [vp, vp, i32, i32, vp, vp]),
     "stp_label_merge": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+    "stp_label_measure": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "stp_label_select_workspace_bytes": (sz, [i32]),
+    "stp_label_select": (i32, [vp, i32, i32, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
 }
 
 _libs = {}          # storage format ("bf16" | "fp16") -> loaded library

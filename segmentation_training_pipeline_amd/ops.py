@@ -570,3 +570,41 @@ def label_merge(rest, nc, nr, h, w, labels, total):
             or any(t.dtype != torch.int32 or t.numel() < 1 for t in (nc, nr, total))):
         raise ValueError("label_merge: two int32 label images of h x w, three int32 counts")
     _lib.call("stp_label_merge", ptr(_dev(rest)), ptr(_dev(nc)), ptr(_dev(nr)), h, w, ptr(_dev(labels)), ptr(_dev(total)), stream())
+
+
+# per-object measurements on the device (csrc/measure.hip): ONE int32 label image [h, w] -> a table per label, the selection by area and
+# confidence
+def label_measure(labels, probs, h, w, C, channel, label_cap, sums, boxes, out_of_range):
+    """``sums`` int64 [label_cap + 1, 4] = (area, sum of y, sum of x, sum of q) and ``boxes`` int32 [label_cap + 1, 4] = the closed box
+    (min y, min x, max y, max x; (h, w, -1, -1) without a pixel) per value 0..label_cap of the int32 image ``labels``; q = (int)(clamp(p,
+    0, 1) * 65535) of ``probs[..., channel]`` (fp32 [h, w, C]; None: no probabilities, q = 0).  ``out_of_range`` int64 [1] = the pixels
+    whose value lies outside 0..label_cap (they count as background)."""
+    if labels.numel() < h * w or labels.dtype != torch.int32:
+        raise ValueError("label_measure: an int32 label image of h x w")
+    if probs is not None and (probs.dtype != torch.float32 or probs.numel() < h * w * max(int(C), 1)):
+        raise ValueError("label_measure: float32 probabilities of h x w x C, or None")
+    if (sums.dtype != torch.int64 or boxes.dtype != torch.int32 or min(sums.numel(), boxes.numel()) < 4 * (int(label_cap) + 1)
+            or out_of_range.dtype != torch.int64 or out_of_range.numel() < 1):
+        raise ValueError("label_measure: int64 sums and int32 boxes [label_cap + 1, 4], an int64 out-of-range count")
+    _lib.call("stp_label_measure", ptr(_dev(labels)), ptr(_dev(probs)), h, w, int(C), int(channel), int(label_cap), ptr(_dev(sums)),
+              ptr(_dev(boxes)), ptr(_dev(out_of_range)), stream())
+
+
+def label_select_workspace_bytes(label_cap):
+    return int(_lib.load().stp_label_select_workspace_bytes(int(label_cap)))
+
+
+def label_select(labels, h, w, label_cap, sums, boxes, min_area, conf_num, conf_den, out_labels, count, out_sums, out_boxes, workspace):
+    """Keeps the labels of ``label_measure``'s table with ``area >= min_area`` (and > 0) and ``sum q * conf_den >= conf_num * 65535 * area``,
+    in order, renumbered 1..count: ``out_labels`` int32 [h, w] (may be ``labels``), ``count`` int32 [1], ``out_sums`` / ``out_boxes`` = rows
+    0..count of the table in the new numbering (room for label_cap + 1 rows; not the input tables)."""
+    if labels.numel() < h * w or out_labels.numel() < h * w or labels.dtype != torch.int32 or out_labels.dtype != torch.int32:
+        raise ValueError("label_select: two int32 label images of h x w")
+    rows = 4 * (int(label_cap) + 1)
+    if (sums.dtype != torch.int64 or out_sums.dtype != torch.int64 or boxes.dtype != torch.int32 or out_boxes.dtype != torch.int32
+            or min(sums.numel(), out_sums.numel(), boxes.numel(), out_boxes.numel()) < rows or count.dtype != torch.int32
+            or count.numel() < 1):
+        raise ValueError("label_select: int64 sums and int32 boxes [label_cap + 1, 4] in and out, an int32 count")
+    _lib.call("stp_label_select", ptr(_dev(labels)), h, w, int(label_cap), ptr(_dev(sums)), ptr(_dev(boxes)), int(min_area), int(conf_num),
+              int(conf_den), ptr(_dev(out_labels)), ptr(_dev(count)), ptr(_dev(out_sums)), ptr(_dev(out_boxes)), ptr(_dev(workspace)),
+              _nbytes(workspace), stream())
