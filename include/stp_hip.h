@@ -861,6 +861,43 @@ int stp_predict_finish(const float* acc, int32_t H, int32_t W, int32_t C, int32_
                        int32_t out_ld, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Sliding-window prediction on the device (csrc/window.hip): an image larger than the network shape is predicted at its own pixel scale
+ * in overlapping H x W windows, cross-faded where they overlap (`windows: <overlap>`, PipelineConfig._predict_windows_device).  Three
+ * kernels around the unchanged inference plan and stp_predict_accumulate.  uint8 and fp32 only (both builds export the same code).  A
+ * window at origin (y0, x0) weights its pixel (ly, lx) with the INTEGER ry[ly] * rx[lx], r[i] = min(i + 1, L - i, overlap + 1); every
+ * fp32 value comes from the operation numpy applies in the host statement (tests/_window_reference.py) - one multiplication and one
+ * addition per window in window order, one correctly rounded division, one multiplication by 255, a truncation - so the results equal
+ * it bit for bit.  No atomics; element indices are int64.  16-byte accesses where the destination rows start on 16-byte boundaries
+ * (aligned base, row pitch a multiple of 16 bytes; stp_window_finish ends such a row with a scalar tail), one element per thread
+ * otherwise; sources are read element by element.  STP_E_BADARG before any launch: a NULL pointer, a size (or k) <= 0, n outside
+ * 1..64, an origin outside the image (y0 < 0, y0 >= h, x0 < 0, x0 >= w), overlap < 0 or 2 * overlap > min(H, W) (or overlap > 4095:
+ * the weight must be an exact fp32 integer), source == destination, out_ld < w, mode outside 0..2, mode 2 with C > 32.
+ *
+ * `origins` is a HOST pointer to n (y0, x0) int32 pairs, copied into the kernel's arguments; more than 64 windows take several calls, in
+ * order.
+ *   stp_window_gather_u8  : dst[i][y][x][c] = img[min(y0_i + y, h - 1)][min(x0_i + x, w - 1)][c] for y < H, x < W: the windows of one batch
+ *                           cut out of the image [h][w][C] into a batch [n][H][W][C] at the network shape; an image smaller than the
+ *                           window is edge-replicated (numpy.pad(mode="edge")).
+ *   stp_window_accumulate : acc = the batch's [n][H][W][C] probability sums.  GATHER form: a thread owns elements of the canvas [h][w][C]
+ *                           and goes through the n windows in index order; for each window that holds its pixel,
+ *                           canvas = canvas + (float)(ry * rx) * acc[i][y - y0][x - x0][c].  No two threads write one element; an
+ *                           element is read and written once per call, however many windows cover it.  The launch covers only the rows
+ *                           the windows span; the other rows are not touched.  The caller zeroes the canvas once per image
+ *                           (stp_zero_bytes).
+ *   stp_window_finish     : value = canvas[y][x][c] / ((float)k * sy[y] * sx[x]); k = how many maps each window's sum holds, sy / sx = DEVICE
+ *                           fp32 tables [h] / [w] of the per-axis sums of the ramps over the windows that hold the row / column (the
+ *                           weight sum of a product grid of windows is separable).  The caller keeps k * max(sy) * max(sx) <= 2^24, so
+ *                           the denominator is an exact integer in any order.  mode and out_ld as stp_predict_finish's: 0 fp32 [h][w][C],
+ *                           1 uint8 (uint8)(value * 255.f), 2 uint8 [h][w] first index of the largest value (a NaN never wins) or,
+ *                           C == 1, value > 0.5f; rows of `out` lie out_ld PIXELS apart. */
+int stp_window_gather_u8(const uint8_t* img, int32_t h, int32_t w, int32_t C, const int32_t* origins, int32_t n, uint8_t* dst, int32_t H,
+                         int32_t W, void* stream);
+int stp_window_accumulate(const float* acc, int32_t H, int32_t W, int32_t C, const int32_t* origins, int32_t n, int32_t overlap,
+                          float* canvas, int32_t h, int32_t w, void* stream);
+int stp_window_finish(const float* canvas, int32_t h, int32_t w, int32_t C, int32_t k, const float* sy, const float* sx, int32_t mode,
+                      void* out, int32_t out_ld, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Masks on the device (csrc/mask.hip): what is done with ONE image's finished fp32 map [h][w][C] (stp_predict_finish mode 0) - threshold,
  * disk erosion / dilation, the run-length code, the counters of a threshold sweep.  uint8, fp32 and integers only (both builds export the
  * same code); all of it exact integer work, equal to the host statement (numpy, scipy.ndimage, segmentation_pipeline/impl/rle.py) bit for

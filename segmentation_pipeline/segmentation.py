@@ -153,6 +153,8 @@ class PipelineConfig(generic.GenericTaskConfig):
         return model
 
     def load_model(self, fold=0, stage=-1):
+        if self.windows is not None:
+            self._check_windows()
         if stage < 0:
             stage = len(self.stages) + stage
         model = self.createNet1(True)
@@ -255,6 +257,8 @@ class PipelineConfig(generic.GenericTaskConfig):
         the item's own size or, ``original_size=False`` and no ``crops``, at the network shape), and, where the items share a size, the
         one tensor [n * h, w, ...] whose row blocks they are (else None).  The mask methods go on from here on the device."""
         from segmentation_training_pipeline_amd import ops
+        if self.windows is not None:
+            return [self._predict_windows_device(models, ttflips, it.x, mode) for it in items], None
         if self.crops:
             return [self._predict_cells_device(models, ttflips, it.x, mode) for it in items], None
         impl0 = _impl(models[0])
@@ -279,6 +283,8 @@ class PipelineConfig(generic.GenericTaskConfig):
         ``original_size=False`` and no ``crops``, at the network shape).  Resize, flips, the sum over models and flips, the mean, the
         way back to the image's size and the quantisation all run on the device; the finished maps of a batch come back in one copy
         when they share a size, one copy per item otherwise."""
+        if self.windows is not None:
+            return [self._predict_windows(models, ttflips, it.x, mode) for it in items]
         if self.crops:
             return [self._predict_cells(models, ttflips, it.x, mode) for it in items]
         maps, whole = self._predict_maps_device(models, ttflips, items, mode, original_size)
@@ -288,6 +294,8 @@ class PipelineConfig(generic.GenericTaskConfig):
 
     def _predict_batches(self, spath, fold, stage, limit, ttflips, mode=0, original_size=True, device=False):
         from segmentation_pipeline.impl.datasets import DirectoryDataSet
+        if self.windows is not None:
+            self._check_windows()
         nets_ = self._models(fold, stage)
         ds = DirectoryDataSet(spath)
         n = len(ds) if limit < 0 else min(limit, len(ds))
@@ -300,10 +308,10 @@ class PipelineConfig(generic.GenericTaskConfig):
                 yield items, self._predict_maps(nets_, ttflips, items, mode, original_size)
 
     def predict_on_directory(self, spath, fold=0, stage=0, limit=-1, batch_size=32, ttflips=False):
-        """Yields (items, probabilities) per batch: a float32 array [n, H, W, classes] at the network shape, or - ``crops`` - the
-        list of the items' assembled maps at their own sizes."""
+        """Yields (items, probabilities) per batch: a float32 array [n, H, W, classes] at the network shape, or - ``crops`` or
+        ``windows`` - the list of the items' assembled maps at their own sizes."""
         for items, maps in self._predict_batches(spath, fold, stage, limit, ttflips, self.PROBS, original_size=False):
-            yield items, (maps if self.crops else np.stack(maps))
+            yield items, (maps if self.crops or self.windows is not None else np.stack(maps))
 
     def _predict_cells(self, models, ttflips, img, mode=0):
         """``crops: N`` at prediction time (README.md:488-491): the image is split into the N x N cells the model was trained
@@ -332,6 +340,99 @@ class PipelineConfig(generic.GenericTaskConfig):
                                    cell.shape[0], cell.shape[1], out_ld=w)
         return out
 
+    # ---------------------------------------------------------------- sliding windows (csrc/window.hip; `windows: <overlap>`)
+    @staticmethod
+    def window_origins(size, L, overlap):
+        """Origins of the windows of length ``L`` along one axis of ``size`` pixels: stride ``L - overlap``, the last window shifted
+        back so that it ends at the image's edge; ``[0]`` where one window holds the axis."""
+        size, L, overlap = int(size), int(L), int(overlap)
+        if size <= L:
+            return [0]
+        return list(range(0, size - L, L - overlap)) + [size - L]
+
+    @staticmethod
+    def window_ramp(L, overlap):
+        """int64 [L]: the cross-fade weight ``min(i + 1, L - i, overlap + 1)`` of a window's pixel i along one axis."""
+        i = np.arange(int(L), dtype=np.int64)
+        return np.minimum(np.minimum(i + 1, int(L) - i), int(overlap) + 1)
+
+    @staticmethod
+    def window_sums(size, L, overlap):
+        """int64 [size]: per pixel of one axis, the sum of the ramps of the windows that hold it.  The windows of an image form a
+        product grid and a window's weight is ``ramp_y * ramp_x``, so the weight sum of pixel (y, x) is ``sy[y] * sx[x]``."""
+        ramp = PipelineConfig.window_ramp(L, overlap)
+        sums = np.zeros(int(size), np.int64)
+        for o in PipelineConfig.window_origins(size, L, overlap):
+            n = min(int(L), int(size) - o)
+            sums[o:o + n] += ramp[:n]
+        return sums
+
+    WINDOW_WEIGHT_LIMIT = 2 ** 24      # k * sy * sx stays an exact float32 integer
+
+    def _check_windows(self, k=None, size=None):
+        """The ``windows`` key, checked before anything is loaded: an integer overlap of at most half the network shape, not
+        together with ``crops``; with ``k`` (maps summed per window) and an image ``size``: every denominator ``k * sy[y] * sx[x]``
+        is an integer that float32 holds exactly."""
+        v = self.windows
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("windows: the overlap of neighbouring windows in pixels, an integer: got %r" % (v,))
+        H, W = int(self.shape[0]), int(self.shape[1])
+        if not 0 <= v <= min(H, W) // 2:
+            raise ValueError("windows: %d is outside 0..%d (half the network shape %d x %d)" % (v, min(H, W) // 2, H, W))
+        if self.crops is not None:
+            raise ValueError("windows and crops are two ways to predict a large image: set one (windows: %r, crops: %r)" % (v, self.crops))
+        if k is not None:
+            top = int(k) * int(self.window_sums(size[0], H, v).max()) * int(self.window_sums(size[1], W, v).max())
+            if top > self.WINDOW_WEIGHT_LIMIT:
+                raise ValueError("windows: %d with %d maps per window gives a weight sum of %d, above 2**24: float32 would round it"
+                                 % (v, k, top))
+
+    def _predict_windows(self, models, ttflips, img, mode=0):
+        """``windows: <overlap>`` at prediction time: the image is predicted at its own pixel scale in overlapping windows of the
+        network shape, cross-faded where they overlap - no resize, no seams.  All of it runs on the device; one copy brings the
+        finished map (``mode``: PROBS / BYTES / LABELS, at the image's size) back."""
+        return self._predict_windows_device(models, ttflips, img, mode).cpu().numpy()
+
+    def _predict_windows_device(self, models, ttflips, img, mode=0):
+        """The finished map of ``_predict_windows``, left on the device.  The image goes to the device once; its windows are taken in
+        raster order in chunks of the inference batch: stp_window_gather_u8 cuts a chunk into a batch at the network shape,
+        ``predict_on_batch_device`` sums the fold models' (and flips') probabilities, stp_window_accumulate adds the ramp-weighted
+        sums into the full-size canvas in window order; stp_window_finish divides by the weight sum."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        models = models if isinstance(models, (list, tuple)) else [models]
+        impl0 = _impl(models[0])
+        H, W, ch = impl0.H, impl0.W, impl0.in_ch
+        img = np.asarray(img)
+        if img.ndim == 2:
+            img = img[:, :, None]
+        if img.shape[2] < ch:      # (the channels as _resize_to_net prepares them: grey repeated, extra bands cut)
+            if img.shape[2] != 1:
+                raise ValueError("image has %d channels, the network expects %d" % (img.shape[2], ch))
+            img = np.repeat(img, ch, axis=2)
+        img = np.ascontiguousarray(img[:, :, :ch], dtype=np.uint8)
+        h, w = img.shape[:2]
+        self._check_windows(len(models) * (3 if ttflips else 1), (h, w))
+        ov, classes = int(self.windows), int(self.classes)
+        origins = [(y0, x0) for y0 in self.window_origins(h, H, ov) for x0 in self.window_origins(w, W, ov)]
+        dev = impl0.device
+        src = torch.from_numpy(img).to(dev)
+        sy = torch.from_numpy(self.window_sums(h, H, ov).astype(np.float32)).to(dev)
+        sx = torch.from_numpy(self.window_sums(w, W, ov).astype(np.float32)).to(dev)
+        xs = torch.empty((impl0.batch, H, W, ch), dtype=torch.uint8, device=dev)
+        numel = h * w * classes
+        canvas = torch.empty(-(-numel // 4) * 4, dtype=torch.float32, device=dev)      # (stp_zero_bytes clears whole 16-byte words)
+        ops.zero_bytes(canvas, canvas.numel() * 4)
+        k = 0
+        for s in range(0, len(origins), impl0.batch):
+            chunk = origins[s:s + impl0.batch]
+            ops.window_gather_u8(src, h, w, ch, chunk, xs, H, W)
+            acc, k = self.predict_on_batch_device(models, ttflips, xs, len(chunk))
+            ops.window_accumulate(acc, H, W, classes, chunk, ov, canvas, h, w)
+        out = self._new_map(acc, mode, h, w)
+        ops.window_finish(canvas, h, w, classes, k, sy, sx, mode, out)
+        return out
+
     def predict_to_directory(self, spath, tpath, fold=0, stage=0, limit=-1, batchSize=32, binaryArray=False, ttflips=False, labelMap=False):
         """Writes one prediction per image of ``spath`` into ``tpath``: ``<stem>.png`` = probability of channel 0 as bytes (a
         multi-label head: ``<stem>_<c>.png`` per class), ``binaryArray``: ``<stem>.npy`` = float32 H x W x classes.
@@ -343,6 +444,8 @@ class PipelineConfig(generic.GenericTaskConfig):
                              "independent maps - write them with labelMap=False" % self.classes)
         if labelMap and binaryArray:
             raise ValueError("labelMap writes PNGs of class indices, binaryArray writes float32 arrays: choose one")
+        if self.windows is not None:
+            self._check_windows()
         os.makedirs(tpath, exist_ok=True)
         from PIL import Image
         mode = self.LABELS if labelMap else (self.PROBS if binaryArray else self.BYTES)
@@ -392,6 +495,8 @@ class PipelineConfig(generic.GenericTaskConfig):
     def _mask_mode(self, threshold, opening, closing, channel, min_size=0, area_threshold=0):
         """stp_mask_threshold's mode for this head (0: sigmoid map > threshold, 1: softmax argmax == channel), after the argument checks
         every mask method makes before a model is loaded."""
+        if self.windows is not None:
+            self._check_windows()
         if not 0 <= int(channel) < int(self.classes):
             raise ValueError("channel %r: the head has %d class(es)" % (channel, self.classes))
         for name, r in (("opening", opening), ("closing", closing)):

@@ -382,6 +382,55 @@ def predict_finish(acc, H, W, Cn, k, mode, out, h, w, out_ld=None):
     _lib.call("stp_predict_finish", ptr(_dev(acc)), H, W, Cn, int(k), int(mode), ptr(_dev(out)), h, w, out_ld, stream())
 
 
+# sliding-window prediction on the device (csrc/window.hip): ``origins`` is a HOST sequence of (y0, x0) pairs; an entry point takes up to
+# 64 windows, a longer sequence goes down in slices of 64, in order
+WINDOWS_PER_CALL = 64
+
+
+def _origin_slices(origins):
+    flat = [(int(y0), int(x0)) for y0, x0 in origins]
+    for s in range(0, len(flat), WINDOWS_PER_CALL):
+        part = flat[s:s + WINDOWS_PER_CALL]
+        yield s, len(part), (C.c_int32 * (2 * len(part)))(*[v for yx in part for v in yx])
+
+
+def window_gather_u8(img, h, w, Cn, origins, dst, H, W):
+    """``dst`` uint8 [n, H, W, Cn] = the windows of the uint8 image ``img`` [h, w, Cn] at ``origins``, coordinates clipped to the image."""
+    if not len(origins) or img.numel() < h * w * Cn or dst.numel() < len(origins) * H * W * Cn:
+        raise ValueError("window_gather_u8: no window, or buffers smaller than the image / n x H x W x C")
+    if img.dtype != torch.uint8 or dst.dtype != torch.uint8:
+        raise ValueError("window_gather_u8: uint8 in, uint8 out")
+    flat = _dev(dst).view(-1)
+    for s, n, org in _origin_slices(origins):
+        _lib.call("stp_window_gather_u8", ptr(_dev(img)), h, w, Cn, org, n, ptr(flat[s * H * W * Cn:]), H, W, stream())
+
+
+def window_accumulate(acc, H, W, Cn, origins, overlap, canvas, h, w):
+    """``canvas`` fp32 [h, w, Cn] += the ramp-weighted sums ``acc`` fp32 [n, H, W, Cn] of the windows at ``origins``, in their order."""
+    if not len(origins) or acc.numel() < len(origins) * H * W * Cn or canvas.numel() < h * w * Cn:
+        raise ValueError("window_accumulate: no window, or buffers smaller than n x H x W x C / the canvas")
+    if acc.dtype != torch.float32 or canvas.dtype != torch.float32:
+        raise ValueError("window_accumulate: float32 in, float32 out")
+    flat = _dev(acc).view(-1)
+    for s, n, org in _origin_slices(origins):
+        _lib.call("stp_window_accumulate", ptr(flat[s * H * W * Cn:]), H, W, Cn, org, n, int(overlap), ptr(_dev(canvas)), h, w, stream())
+
+
+def window_finish(canvas, h, w, Cn, k, sy, sx, mode, out, out_ld=None):
+    """``out`` (fp32 for mode 0, uint8 for 1: bytes, 2: labels; ``out_ld`` pixels per row) = ``canvas / (k * sy[y] * sx[x])``, finished as
+    ``predict_finish`` finishes a map; ``sy`` / ``sx``: fp32 device tables of the per-axis weight sums."""
+    out_ld = w if out_ld is None else int(out_ld)
+    per_px = 1 if mode == 2 else Cn
+    room = out.untyped_storage().nbytes() // out.element_size() - out.storage_offset()      # elements from the corner to the storage's end
+    if canvas.numel() < h * w * Cn or sy.numel() < h or sx.numel() < w or (out_ld >= w and room < ((h - 1) * out_ld + w) * per_px):
+        raise ValueError("window_finish: buffers are smaller than the maps")
+    if canvas.dtype != torch.float32 or sy.dtype != torch.float32 or sx.dtype != torch.float32:
+        raise ValueError("window_finish: a float32 canvas and float32 weight sums")
+    if mode in (0, 1, 2) and out.dtype != (torch.float32 if mode == 0 else torch.uint8):
+        raise ValueError("window_finish: mode %d writes %s" % (mode, "float32" if mode == 0 else "uint8"))
+    _lib.call("stp_window_finish", ptr(_dev(canvas)), h, w, Cn, int(k), ptr(_dev(sy)), ptr(_dev(sx)), int(mode), ptr(_dev(out)), out_ld, stream())
+
+
 # masks on the device (csrc/mask.hip): ONE image's finished fp32 map [h, w, Cn] -> uint8 {0, 1} masks, their run-length code, sweep counters
 def mask_threshold(probs, h, w, Cn, channel, mode, threshold, out, out_ld=None):
     """``out`` uint8 [h, out_ld]: mode 0 ``probs[:, :, channel] > float32(threshold)``, mode 1 ``argmax == channel`` (first largest)."""

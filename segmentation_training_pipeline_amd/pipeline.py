@@ -23,7 +23,7 @@ from .backend import class_metric_names, confusion_metrics, is_class_metric
 # YAML keys flagged (meta.custom) in schemas/segmentation.raml:26-120 (+ the keys used by the examples that
 # the RAML does not list): consumed by the pipeline, never forwarded to the model constructor.
 CUSTOM_KEYS = {
-    "architecture", "crops", "augmentation", "transforms", "optimizer", "lr", "clipnorm", "clipvalue", "loss", "batch",
+    "architecture", "crops", "windows", "augmentation", "transforms", "optimizer", "lr", "clipnorm", "clipvalue", "loss", "batch",
     "metrics", "primary_metric", "primary_metric_mode", "callbacks", "stages", "folds_count", "random_state",
     "extra_train_data", "dataset_augmenter", "classifier", "classifier_lr", "testSplit", "dataset", "datasets", "fit_with",
     "imports", "import_tasks", "run_tasks", "copyWeights", "dtype", "loss_scale", "gpus", "inference_batch", "testTimeAugmentation",
@@ -872,6 +872,7 @@ class GenericTaskConfig(object):
         self.classes = int(a.get("classes", 1))
         self.shape = a.get("shape")
         self.crops = a.get("crops")
+        self.windows = a.get("windows")              # sliding-window prediction: the overlap in pixels, None = off (a key of this backend)
         self.batch = int(a.get("batch", 16))
         self.optimizer = a.get("optimizer", "Adam")
         self.lr = float(a.get("lr", 0.001))
