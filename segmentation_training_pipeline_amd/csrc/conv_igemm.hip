@@ -820,7 +820,8 @@ extern "C" int stp_conv2d(const stp_conv_params* p, void* stream) {
       a.divCpt = make_fastdiv((uint32_t)a.zcpt);
     }
     if (p->fold_src) {      // folded shortcut data gradient: only on this path, 3x3 / pad 1 geometry, equal channel counts
-      if (!a.zperm || !fold_geometry_ok(a) || !p->fold_weight || p->fold_C != a.C0) return STP_E_BADARG;
+      // (p->tile != 0: stp_conv2d_fold_ok answers 0 for a forced tile, and the header refuses whatever it answers 0 for)
+      if (p->tile != 0 || !a.zperm || !fold_geometry_ok(a) || !p->fold_weight || p->fold_C != a.C0) return STP_E_BADARG;
       const int64_t bf = (int64_t)a.N * a.Hs0 * a.Ws0 * a.C0 * (p->dtype == STP_H16 ? 2 : 4), bwf = (int64_t)a.wrows * a.C0 * (p->dtype == STP_H16 ? 2 : 4);
       if (bf >= (1ll << 31) || bwf >= (1ll << 31)) return STP_E_BADARG;
       a.fold_src = (const char*)p->fold_src; a.fold_weight = (const char*)p->fold_weight; a.fold_cpt = a.C0 / ke;

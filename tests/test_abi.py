@@ -83,7 +83,6 @@ UNNAMED_ENTRY_POINTS = {
     "stp_calib_mfma": "calibration: MFMA peak",
     "stp_calib_copy": "calibration: copy bandwidth",
     # host-side queries
-    "stp_conv2d_fold_ok": "query: whether the plan may fold a shortcut (exercised through graph.Plan in the step tests)",
     "stp_wgrad_sc_slabs": "query: slab count of the small-channel weight gradient (read by stp_conv2d_wgrad_workspace_bytes)",
     "stp_wgrad_group_table_bytes": "query: used by ops.WgradGroup, which the grouped weight-gradient tests construct",
     "stp_wgrad_group_workspace_bytes": "query: used by ops.WgradGroup",
