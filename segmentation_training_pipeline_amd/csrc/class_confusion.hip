@@ -4,7 +4,7 @@
 //   stp_class_confusion     rows [pixels][ldc] at the mask's resolution
 //   stp_class_confusion_ignore  the same with an ignore label: pixels whose target holds it are not counted
 //   stp_class_confusion_up  logits held at 1 / f of it (where stp_softmax_cce_dice_up removed the resized tensor from the step): every output
-//                           pixel is interpolated with the expression of resize_bilinear_kernel (bn_pool.hip) and rounded to the storage
+//                           pixel is interpolated with the expression of resize_bilinear_kernel (resize.hip) and rounded to the storage
 //                           type as that kernel's store rounds it - the counts are those of stp_resize_bilinear + stp_class_confusion.
 // One thread per pixel; a workgroup (1024 threads, so that few tables leave the chip) keeps the classes^2 table in LDS.  Masks are
 // piecewise constant: the 64 pixels of a wave mostly share one (target, predicted) key, so a wave first peels off up to CONF_PEEL distinct

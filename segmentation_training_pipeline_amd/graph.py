@@ -681,7 +681,7 @@ class Plan(object):
 
     def conv3x3_taps(self, name, x, Cout, bias=False):
         """``Conv2D(Cout, 3x3, padding 1)`` with few output channels over many input channels (the class heads of FPN / PSPNet: 512 -> 3 /
-        20) as a 1x1 convolution into 9 x Cout tap channels + stp_tapsum_fwd (bn_pool.hip: W_t . shift_t(x) = shift_t(W_t . x)).  The
+        20) as a 1x1 convolution into 9 x Cout tap channels + stp_tapsum_fwd (elementwise.hip: W_t . shift_t(x) = shift_t(W_t . x)).  The
         parameters keep the layer's names and shapes (``name/kernel`` = (Cout, 3, 3, Cin), ``name/bias``): the 1x1 launch reads the 3x3
         kernel's own bytes as [9 Cout][Cin], its weight gradient IS the kernel's gradient."""
         cin = x.meta.get("real_c", x.C)

@@ -1,5 +1,5 @@
 """GPU op tests of csrc/deeplab.hip (depthwise convolution and its two gradients, align-corners resize and its gradient, element
-dropout, sigmoid activation and its gradient) and of the ReLU6 BatchNormalization (relu = 2 of bn_pool.hip / common.h), in fp32 and in
+dropout, sigmoid activation and its gradient) and of the ReLU6 BatchNormalization (relu = 2 of bn.hip / common.h), in fp32 and in
 both 16-bit builds.  Each C-ABI entry point is called directly and compared with the float64 numpy restatement of
 tests/_deeplab_reference.py - never with a second run of a kernel, and with no tolerance derived from a kernel's output:
 
