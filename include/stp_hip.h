@@ -861,6 +861,28 @@ int stp_predict_finish(const float* acc, int32_t H, int32_t W, int32_t C, int32_
                        int32_t out_ld, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Dihedral (D4) test-time augmentation on the device (csrc/dihedral.hip; `ttflips="d4"`): all eight symmetries of the square where
+ * stp_flip_u8 / stp_predict_accumulate have three.  uint8 and fp32 only (both builds export the same code); values are moved as they
+ * are or added with one fp32 add, so the results equal the numpy statement (tests/_dihedral_reference.py) bit for bit.  No atomics;
+ * element indices are int64; nothing outside the N * H * W * C elements of the destination is written.
+ *
+ * op 0..7, on x [N][H][W][C] (whole pixels move, channels keep their order):
+ *   g_op(x)   = x.transpose(0, 2, 1, 3) if op & 4, then columns reversed if op & 1, then rows reversed if op & 2
+ *               -> [N][H'][W'][C], (H', W') = (W, H) if op & 4 else (H, W)
+ *   inv_op(y) = rows reversed if op & 2, then columns reversed if op & 1, then transposed if op & 4: inv_op(g_op(x)) == x.
+ * 0, 1, 2 are stp_flip_u8's flips; 3 is the half turn, 4 the transpose, 5 and 6 the quarter turns, 7 the anti-transpose.  H != W is
+ * legal here (the layer above offers the transposing ops for square network shapes only).
+ *   stp_dihedral_u8                 : dst[N][H'][W'][C] = g_op(src[N][H][W][C]).
+ *   stp_predict_accumulate_dihedral : acc[N][H][W][C] += inv_op(probs), probs being [N][H'][W'][C]: one __fadd_rn per element; the
+ *                                     caller zeroes acc.
+ * The transposing ops move tiles of 8 to 64 pixels a side through LDS (pixels below 256 bytes; rows of the source tile are read and rows
+ * of the destination tile are written as contiguous runs) or gather whole pixels (256 bytes and more).  16-byte accesses where both
+ * bases are 16-byte aligned and the row pitches are multiples of 16 bytes, one element per thread otherwise.  STP_E_BADARG before any
+ * launch: a NULL pointer, a size <= 0, op outside 0..7, source == destination, W * C or H * C above 2^31 - 1. */
+int stp_dihedral_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t C, int32_t op, void* stream);
+int stp_predict_accumulate_dihedral(const float* probs, float* acc, int32_t N, int32_t H, int32_t W, int32_t C, int32_t op, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Sliding-window prediction on the device (csrc/window.hip): an image larger than the network shape is predicted at its own pixel scale
  * in overlapping H x W windows, cross-faded where they overlap (`windows: <overlap>`, PipelineConfig._predict_windows_device).  Three
  * kernels around the unchanged inference plan and stp_predict_accumulate.  uint8 and fp32 only (both builds export the same code).  A

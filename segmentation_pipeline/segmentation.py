@@ -197,31 +197,85 @@ class PipelineConfig(generic.GenericTaskConfig):
             ops.augment_u8(src, None, xs[i:i + 1], None, prm, 1, h, w, H, W, ch)
         return xs if device else xs.cpu().numpy()
 
+    TTA_VALUES = "None / False (no augmentation), True (the two flips), 'd4' (the eight symmetries of the square)"
+
+    @staticmethod
+    def _tta_ops(ttflips):
+        """The members of the square's symmetry group a ``ttflips`` value sums, in the order they are added: ``None`` / ``False``
+        ``(0,)``, ``True`` (and any other non-string truthy value) ``(0, 1, 2)``, ``"d4"`` ``(0, ..., 7)``.  Member ``op`` is:
+        transpose if ``op & 4``, then columns reversed if ``op & 1``, then rows reversed if ``op & 2`` (``_d4_apply``)."""
+        if isinstance(ttflips, str):
+            if ttflips != "d4":
+                raise ValueError("ttflips %r: the accepted values are %s" % (ttflips, PipelineConfig.TTA_VALUES))
+            return tuple(range(8))
+        return (0, 1, 2) if ttflips else (0,)
+
+    @staticmethod
+    def _d4_apply(x, op):
+        """Member ``op`` of the group on [n, H, W, C] (numpy view): whole pixels move, channels keep their order."""
+        t = x.transpose(0, 2, 1, 3) if op & 4 else x
+        t = t[:, :, ::-1] if op & 1 else t
+        return t[:, ::-1] if op & 2 else t
+
+    @staticmethod
+    def _d4_invert(y, op):
+        """The inverse of ``_d4_apply(., op)``: the same steps undone in reverse order."""
+        u = y[:, ::-1] if op & 2 else y
+        u = u[:, :, ::-1] if op & 1 else u
+        return u.transpose(0, 2, 1, 3) if op & 4 else u
+
+    def _check_tta(self, ttflips):
+        """The ``ttflips`` value, checked before anything is loaded -> its ops.  ``"d4"`` holds transposing members: the network
+        shape (after the ``crops`` division) has to be square."""
+        ops_ = self._tta_ops(ttflips)
+        if len(ops_) == 8:
+            c = int(self.crops) if self.crops is not None else 1
+            H, W = int(self.shape[0]) // c, int(self.shape[1]) // c
+            self._d4_needs_square(H, W)
+        return ops_
+
+    @staticmethod
+    def _d4_needs_square(H, W):
+        if H != W:
+            raise ValueError("ttflips='d4': the transposing members of the group need H == W and the network shape is %d x %d; "
+                             "ttflips=True (the two flips) remains available" % (H, W))
+
     def predict_on_batch(self, models, ttflips, xs):
-        """Mean of the fold models' probabilities, optionally with flip test-time augmentation (README.md:519-534).
-        ``models``: one model or a list; ``xs``: uint8 [n, H, W, 3] at the network shape, n <= inference batch.
+        """Mean of the fold models' probabilities, optionally with flip test-time augmentation (README.md:519-534) or, ``"d4"``, with
+        all eight symmetries of the square (``_tta_ops``).  ``models``: one model or a list; ``xs``: uint8 [n, H, W, 3] at the network
+        shape, n <= inference batch.
         Numpy in, numpy out: the host statement of what ``predict_on_batch_device`` + stp_predict_finish compute on the device."""
         models = models if isinstance(models, (list, tuple)) else [models]
         acc = np.zeros((len(xs),) + tuple(xs.shape[1:3]) + (self.classes,), np.float32)
         k = 0
         for m in models:
-            acc += m.predict(xs); k += 1
-            if ttflips:
-                acc += m.predict(xs[:, :, ::-1])[:, :, ::-1]; k += 1
-                acc += m.predict(xs[:, ::-1])[:, ::-1]; k += 1
+            for op in self._tta_ops(ttflips):
+                acc += self._d4_invert(m.predict(self._d4_apply(xs, op)), op); k += 1
         return acc / k
 
     def predict_on_batch_device(self, models, ttflips, xs_dev, n):
         """``predict_on_batch`` without the host: ``xs_dev`` is a uint8 device tensor [batch, H, W, C] at the network shape whose first
         ``n`` images count.  Returns ``(acc, k)``: the float32 device SUM [batch, H, W, classes] of the k probability maps (models in
         order, each plain, then - ``ttflips`` - from the column-flipped and from the row-flipped input, un-flipped:
-        stp_predict_accumulate) - the same additions in the same order as the host loop, so ``acc[:n] / k`` is its result bit for bit.
+        stp_predict_accumulate; then - ``"d4"`` - from the other five members of the square's symmetry group, un-transformed:
+        stp_predict_accumulate_dihedral) - the same additions in the same order as the host loop, so ``acc[:n] / k`` is its result
+        bit for bit.
         ``acc`` is this config's one accumulator of that shape: it is zeroed and reused by the next call; stp_predict_finish turns an
         image's slice into the finished map."""
+        for acc, k in self._sum_maps_device(models, ttflips, xs_dev, n):
+            pass
+        return acc, k
+
+    def _sum_maps_device(self, models, ttflips, xs_dev, n):
+        """The additions of ``predict_on_batch_device`` as a generator: yields ``(acc, k)`` after each of them (``find_tta`` reads
+        the running sum on the way; stp_predict_finish does not modify it)."""
         from segmentation_training_pipeline_amd import ops
         import torch
+        tta = self._tta_ops(ttflips)
         impls = [_impl(m) for m in (models if isinstance(models, (list, tuple)) else [models])]
         i0 = impls[0]
+        if len(tta) == 8:
+            self._d4_needs_square(i0.H, i0.W)
         key = (str(i0.device), i0.batch, i0.H, i0.W, int(self.classes))
         cache = self.__dict__.setdefault("_accumulators", {})
         numel = int(np.prod(key[1:]))
@@ -231,10 +285,14 @@ class PipelineConfig(generic.GenericTaskConfig):
         acc = cache[key][:numel].view(key[1:])
         k = 0
         for impl in impls:
-            for flip in ((0, 1, 2) if ttflips else (0,)):
+            for flip in tta:
                 probs = impl.predict_device(xs_dev, n, flip)
-                ops.predict_accumulate(probs, acc, int(n), i0.H, i0.W, int(self.classes), flip); k += 1
-        return acc, k
+                if flip < 3:
+                    ops.predict_accumulate(probs, acc, int(n), i0.H, i0.W, int(self.classes), flip)
+                else:
+                    ops.predict_accumulate_dihedral(probs, acc, int(n), i0.H, i0.W, int(self.classes), flip)
+                k += 1
+                yield acc, k
 
     @staticmethod
     def _scale_back(p, h, w):
@@ -296,6 +354,7 @@ class PipelineConfig(generic.GenericTaskConfig):
         from segmentation_pipeline.impl.datasets import DirectoryDataSet
         if self.windows is not None:
             self._check_windows()
+        self._check_tta(ttflips)
         nets_ = self._models(fold, stage)
         ds = DirectoryDataSet(spath)
         n = len(ds) if limit < 0 else min(limit, len(ds))
@@ -412,7 +471,7 @@ class PipelineConfig(generic.GenericTaskConfig):
             img = np.repeat(img, ch, axis=2)
         img = np.ascontiguousarray(img[:, :, :ch], dtype=np.uint8)
         h, w = img.shape[:2]
-        self._check_windows(len(models) * (3 if ttflips else 1), (h, w))
+        self._check_windows(len(models) * len(self._tta_ops(ttflips)), (h, w))
         ov, classes = int(self.windows), int(self.classes)
         origins = [(y0, x0) for y0 in self.window_origins(h, H, ov) for x0 in self.window_origins(w, W, ov)]
         dev = impl0.device
@@ -446,6 +505,7 @@ class PipelineConfig(generic.GenericTaskConfig):
             raise ValueError("labelMap writes PNGs of class indices, binaryArray writes float32 arrays: choose one")
         if self.windows is not None:
             self._check_windows()
+        self._check_tta(ttflips)
         os.makedirs(tpath, exist_ok=True)
         from PIL import Image
         mode = self.LABELS if labelMap else (self.PROBS if binaryArray else self.BYTES)
@@ -475,6 +535,7 @@ class PipelineConfig(generic.GenericTaskConfig):
     def evaluateAll(self, ds, fold, stage=-1, negatives="real", ttflips=None):
         """Iterator over validation batches of ``fold`` (reference :158-191): each carries the original ``images``,
         ``data`` (ids), ``segmentation_maps`` (ground truth) and ``predicted_maps_aug`` (probabilities, original size)."""
+        self._check_tta(ttflips)
         folds = self.kfold(ds, range(0, len(ds)))
         indexes = [int(i) for i in folds.sampledIndexes(fold, False, negatives)]
         m = self.load_model(fold, stage)
@@ -609,6 +670,7 @@ class PipelineConfig(generic.GenericTaskConfig):
         ``impl.rle.multi_rle_encode(mask[:, :, None])``, ``[]`` for an empty mask - or, ``rle=False``, ``(file_name, int32 h x w label
         image)`` in scipy.ndimage.label's numbering.  Only the runs (or the mask, or the labels) come back."""
         mode = self._mask_mode(threshold, opening, closing, channel, min_size, area_threshold)      # (refusals fire here, not at the first next())
+        self._check_tta(ttflips)
 
         def masks():
             for items, maps in self._predict_batches(spath, fold, stage, limit, ttflips, self.PROBS, device=True):
@@ -673,6 +735,7 @@ class PipelineConfig(generic.GenericTaskConfig):
             raise ValueError("average %r: 'image' or 'pixels'" % (average,))
         if not 0 <= int(channel) < int(self.classes):
             raise ValueError("channel %r: the head has %d class(es)" % (channel, self.classes))
+        self._check_tta(ttflips)
         thresholds = [d / 20 for d in range(1, 20)] if thresholds is None else [float(t) for t in thresholds]
         t32 = np.asarray(thresholds, np.float32)            # what the device compares with
         if not 1 <= len(thresholds) <= 64:
@@ -705,6 +768,70 @@ class PipelineConfig(generic.GenericTaskConfig):
             scores = self.sweep_score(metric, counts[:, :, 0], counts[:, :, 1], totals[:, :1]).mean(axis=0)
         table = {t: float(v) for t, v in zip(thresholds, scores)}
         return thresholds[int(np.argmax(scores))], table
+
+    def find_tta(self, ds, fold, stage=-1, negatives="real", threshold=0.5, metric="dice", average="image", channel=0):
+        """Whether test-time augmentation pays for this model: the ``find_threshold`` score (same items, formulas, ``metric`` and
+        ``average``) of the masks ``map[..., channel] > threshold`` predicted with ``ttflips`` = ``False``, ``True`` and ``"d4"``.  The
+        eight passes run ONCE per batch; the running sum is read after member 1 (k = 1), member 3 (k = 3) and member 8 (k = 8) - each
+        read is stp_predict_finish to the image's size (it leaves the accumulator as it is) and one stp_threshold_counts - so every
+        entry equals ``find_threshold(..., ttflips=v, thresholds=[threshold])[1][threshold]`` exactly.  Returns ``(best, {False:
+        score, True: score, "d4": score})``; the first of ``False, True, "d4"`` wins a tie.  One fold; no ``windows`` / ``crops``."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        if self._softmax_head():
+            raise ValueError("find_tta scores thresholded sigmoid maps, as find_threshold: a softmax head has no threshold")
+        if metric not in self.SWEEP_METRICS:
+            raise ValueError("metric %r: one of %s" % (metric, ", ".join(self.SWEEP_METRICS)))
+        if average not in ("image", "pixels"):
+            raise ValueError("average %r: 'image' or 'pixels'" % (average,))
+        if not 0 <= int(channel) < int(self.classes):
+            raise ValueError("channel %r: the head has %d class(es)" % (channel, self.classes))
+        if isinstance(fold, (list, tuple)):
+            raise ValueError("find_tta takes one fold, as find_threshold: got %r" % (fold,))
+        if self.windows is not None or self.crops:
+            raise ValueError("find_tta does not cover `windows` / `crops` configurations yet: compare find_threshold(ttflips=...) calls")
+        self._check_tta("d4")
+        t32 = np.asarray([float(threshold)], np.float32)            # what the device compares with
+        if not np.isfinite(t32).all():
+            raise ValueError("threshold must be finite")
+        folds = self.kfold(ds, range(0, len(ds)))
+        indexes = [int(i) for i in folds.sampledIndexes(fold, False, negatives)]
+        if not indexes:
+            raise ValueError("fold %r has no validation items" % (fold,))
+        m = self.load_model(fold, stage)
+        impl = m.impl
+        dev, B, C = impl.device, impl.batch, int(self.classes)
+        values, reads = (False, True, "d4"), {1: 0, 3: 1, 8: 2}          # the sum after k members is the `values[reads[k]]` prediction
+        counts = torch.empty((3, len(indexes), 1, 2), dtype=torch.int64, device=dev)
+        totals = torch.empty((3, len(indexes), 2), dtype=torch.int64, device=dev)
+        ws = torch.empty(ops.threshold_counts_workspace_bytes(1), dtype=torch.uint8, device=dev)
+        for s in range(0, len(indexes), B):
+            items = [ds[i] for i in indexes[s:s + B]]
+            targets = []
+            for it in items:
+                y = np.asarray(it.y)
+                plane = y if y.ndim == 2 else y[:, :, channel if y.shape[2] > 1 else 0]
+                if plane.shape != tuple(it.x.shape[:2]):
+                    raise ValueError("item %r: a %s mask for a %d x %d image" % ((it.id, plane.shape) + tuple(it.x.shape[:2])))
+                targets.append(torch.from_numpy(np.ascontiguousarray(plane != 0).view(np.uint8)).to(dev))
+            xs = self._resize_to_net(impl, [it.x for it in items], device=True)
+            for acc, k in self._sum_maps_device([m], "d4", xs, len(items)):
+                if k not in reads:
+                    continue
+                for j, (it, target) in enumerate(zip(items, targets)):
+                    h, w = (int(v) for v in it.x.shape[:2])
+                    probs = self._new_map(acc, self.PROBS, h, w)
+                    ops.predict_finish(acc[j], impl.H, impl.W, C, k, self.PROBS, probs, h, w)
+                    ops.threshold_counts(probs, target, h, w, C, channel, t32, counts[reads[k], s + j], totals[reads[k], s + j], ws)
+        counts, totals = counts.cpu().numpy(), totals.cpu().numpy()          # the only copies back: 4 integers per image and read
+        table = {}
+        for v, cn, tt in zip(values, counts, totals):
+            if average == "pixels":
+                score = self.sweep_score(metric, cn[:, :, 0].sum(0), cn[:, :, 1].sum(0), tt[:, 0].sum())
+            else:
+                score = self.sweep_score(metric, cn[:, :, 0], cn[:, :, 1], tt[:, :1]).mean(axis=0)
+            table[v] = float(score[0])
+        return values[int(np.argmax([table[v] for v in values]))], table
 
     # ---------------------------------------------------------------- object-level scores on the device (csrc/object_match.hip)
     OBJECT_METRICS = ("f2", "ap")
@@ -783,6 +910,7 @@ class PipelineConfig(generic.GenericTaskConfig):
         counters stay on the device until the one copy at the end."""
         from segmentation_training_pipeline_amd import ops
         import torch
+        self._check_tta(ttflips)
         folds = self.kfold(ds, range(0, len(ds)))
         indexes = [int(i) for i in folds.sampledIndexes(fold, False, negatives)]
         if not indexes:
@@ -968,6 +1096,7 @@ class PipelineConfig(generic.GenericTaskConfig):
         smaller number on a tie -, and a component without a core stays one object, numbered after the cores.  ``split=0`` is
         ``components=True`` bit for bit.  Unlike a larger ``opening`` this removes no pixel: the objects partition the mask."""
         mode = self._mask_mode(threshold, opening, closing, channel, min_size, area_threshold)      # (refusals fire here, not at the first next())
+        self._check_tta(ttflips)
         c2 = self._split_c2(split)
 
         def instances():
@@ -1139,6 +1268,7 @@ class PipelineConfig(generic.GenericTaskConfig):
         compared exactly as n / 10000) and renumbers them in order.  Yields ``(file_name, codes_or_labels)`` or, ``measure=True``,
         ``(file_name, codes_or_labels, table)`` with ``table`` the ``object_table`` dict of the objects that are left."""
         mode = self._mask_mode(threshold, opening, closing, channel, min_size, area_threshold)      # (refusals fire here, not at the first next())
+        self._check_tta(ttflips)
         c2 = self._split_c2(split)
         min_area, num = self._min_area(min_area), self._conf_num(min_confidence)
         if not (min_area or num or measure):
@@ -1203,6 +1333,7 @@ class PipelineConfig(generic.GenericTaskConfig):
         matches the shared labels as they are).  The counters stay on the device until the one copy at the end."""
         from segmentation_training_pipeline_amd import ops
         import torch
+        self._check_tta(ttflips)
         folds = self.kfold(ds, range(0, len(ds)))
         indexes = [int(i) for i in folds.sampledIndexes(fold, False, negatives)]
         if not indexes:

@@ -214,6 +214,8 @@ SIGNATURES = {
     "stp_flip_u8": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "stp_predict_accumulate": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "stp_predict_finish": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp]),
+    "stp_dihedral_u8": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "stp_predict_accumulate_dihedral": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "stp_window_gather_u8": (i32, [vp, i32, i32, i32, C.POINTER(i32), i32, vp, i32, i32, vp]),
     "stp_window_accumulate": (i32, [vp, i32, i32, i32, C.POINTER(i32), i32, i32, vp, i32, i32, vp]),
     "stp_window_finish": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp]),

@@ -678,9 +678,11 @@ class HipSegModel(object):
 
     def predict_device(self, x_dev, n, flip=0):
         """``predict`` without the host: ``x_dev`` is a uint8 device tensor [batch, H, W, C] whose first ``n`` images count; they go
-        into the inference plan's input flipped by ``flip`` (stp_flip_u8: 0 none, 1 columns reversed, 2 rows reversed), then the
-        weight copies and the forward pass run.  Returns the plan's float32 probabilities [batch, H, W, classes] ON THE DEVICE
-        (``[:n]`` are the batch's; not un-flipped), valid until the next ``predict`` / ``predict_device`` of this model."""
+        into the inference plan's input flipped by ``flip`` (stp_flip_u8: 0 none, 1 columns reversed, 2 rows reversed; 3..7 are the
+        other members of the square's symmetry group, stp_dihedral_u8: ``flip & 4`` transposes first - a square network shape only -,
+        then ``& 1`` reverses the columns and ``& 2`` the rows), then the weight copies and the forward pass run.  Returns the plan's
+        float32 probabilities [batch, H, W, classes] ON THE DEVICE (``[:n]`` are the batch's; not un-transformed), valid until the
+        next ``predict`` / ``predict_device`` of this model."""
         from . import ops
         ip = self._infer_plan()
         xi = ip.inputs["image"].buf
@@ -688,6 +690,13 @@ class HipSegModel(object):
             raise TypeError("predict_device takes a contiguous uint8 tensor on the model's device")
         if tuple(x_dev.shape) != (self.batch, self.H, self.W, self.in_ch) or not 1 <= int(n) <= self.batch:
             raise ValueError("predict_device takes [%d, %d, %d, %d] images and 1 <= n <= %d" % (self.batch, self.H, self.W, self.in_ch, self.batch))
-        ops.flip_u8(x_dev, xi, int(n), self.H, self.W, self.in_ch, flip)
+        if flip in (0, 1, 2):
+            ops.flip_u8(x_dev, xi, int(n), self.H, self.W, self.in_ch, flip)
+        else:
+            if flip not in (3, 4, 5, 6, 7):
+                raise ValueError("flip is 0..7: got %r" % (flip,))
+            if flip & 4 and self.H != self.W:
+                raise ValueError("flip %d transposes the images: the network shape %d x %d is not square" % (flip, self.H, self.W))
+            ops.dihedral_u8(x_dev, xi, int(n), self.H, self.W, self.in_ch, flip)
         ip.run(ip.prep); ip.run(ip.fwd)
         return ip.probs

@@ -369,6 +369,20 @@ def predict_accumulate(probs, acc, N, H, W, Cn, flip):
     _lib.call("stp_predict_accumulate", ptr(_dev(probs)), ptr(_dev(acc)), N, H, W, Cn, int(flip), stream())
 
 
+# dihedral test-time augmentation (csrc/dihedral.hip): op 0..7 = transpose if op & 4, then columns reversed if op & 1, then rows
+# reversed if op & 2; src / acc are [N, H, W, C], dst / probs [N, H', W', C] with (H', W') = (W, H) for the transposing ops
+def dihedral_u8(src, dst, N, H, W, Cn, op):
+    if min(src.numel(), dst.numel()) < N * H * W * Cn:
+        raise ValueError("dihedral_u8: buffers are smaller than N x H x W x C")
+    _lib.call("stp_dihedral_u8", ptr(_dev(src)), ptr(_dev(dst)), N, H, W, Cn, int(op), stream())
+
+
+def predict_accumulate_dihedral(probs, acc, N, H, W, Cn, op):
+    if min(probs.numel(), acc.numel()) < N * H * W * Cn:
+        raise ValueError("predict_accumulate_dihedral: buffers are smaller than N x H x W x C")
+    _lib.call("stp_predict_accumulate_dihedral", ptr(_dev(probs)), ptr(_dev(acc)), N, H, W, Cn, int(op), stream())
+
+
 def predict_finish(acc, H, W, Cn, k, mode, out, h, w, out_ld=None):
     """``acc``: ONE image's [H, W, Cn] sums; ``out``: fp32 (mode 0) or uint8 (1: bytes, 2: labels) whose first element is the map's
     top-left corner - a view into a larger map with ``out_ld`` pixels per row writes a rectangle of it."""
