@@ -194,7 +194,7 @@ int stp_conv2d_sc_eligible(const stp_conv_params* p);
  * one per 8x32 tile, or one per persistent workgroup in the streaming form. */
 int stp_conv2d_sc_stats_tiles(const stp_conv_params* p);
 int stp_conv2d_sc(const stp_conv_params* p, void* stream);
-/* Wide-output form of the small-channel kernel (conv_sc.hip: conv_scw_stream_kernel): 3x3 / stride 1 / pad 1, 32 input channels,
+/* Wide-output form of the small-channel kernel (conv_sc_wide.hip: conv_scw_stream_kernel): 3x3 / stride 1 / pad 1, 32 input channels,
  * 128 output channels split over dst0 (Cd0 channels, a multiple of 32, dst_sum2x2 = 1: low-resolution, optional bnb_x + stats_partial)
  * and dst1 (full resolution); 16-bit storage.  Replaces the generic per-tap data gradient of decoder_stage3_conv1 + stp_upsample2x_bwd
  * (TF: Conv2DBackpropInput + ResizeNearestNeighborGrad + FusedBatchNormGrad's reductions).  stp_conv2d uses it automatically
@@ -202,7 +202,7 @@ int stp_conv2d_sc(const stp_conv_params* p, void* stream);
 int stp_conv2d_scw_eligible(const stp_conv_params* p);
 int stp_conv2d_scw_stats_tiles(const stp_conv_params* p);
 int stp_conv2d_scw(const stp_conv_params* p, void* stream);
-/* Narrow-output form (conv_sc.hip: conv_scn_stream_kernel): the FORWARD of Conv2D(32, 3x3)(Concatenate([UpSampling2D(2)(x), skip])) with 64 + 64
+/* Narrow-output form (conv_sc_narrow.hip: conv_scn_stream_kernel): the FORWARD of Conv2D(32, 3x3)(Concatenate([UpSampling2D(2)(x), skip])) with 64 + 64
  * input channels (src0 = x at half resolution, src0_mode = STP_SRC_NEAREST2X, src1 = skip), 16-bit storage: both halos resident in LDS (x as its
  * low-resolution pixels), all weights in registers, one wave per SIMD.  Takes `weight` (the plain forward copy [32][3][3][128]); weight_up is
  * ignored.  bias / relu / accumulate0 / stats_partial as for stp_conv2d.  stp_conv2d uses it automatically (tile id 704; STP_SCN=0 switches it
@@ -210,10 +210,10 @@ int stp_conv2d_scw(const stp_conv_params* p, void* stream);
 int stp_conv2d_scn_eligible(const stp_conv_params* p);
 int stp_conv2d_scn_stats_tiles(const stp_conv_params* p);
 int stp_conv2d_scn(const stp_conv_params* p, void* stream);
-/* 64 -> 64 channels, 3x3 / stride 1 / pad 1, 16-bit storage, single source and destination (conv_sc.hip: conv_s64_stream_kernel; ResNet stage 1
+/* 64 -> 64 channels, 3x3 / stride 1 / pad 1, 16-bit storage, single source and destination (conv_sc_s64.hip: conv_s64_stream_kernel; ResNet stage 1
  * forward and data gradient): the whole weight matrix in the registers of every wave, the halo double-buffered in LDS.  residual, or stats_partial,
  * or bnb_x + stats_partial; no bias / relu / accumulate.  OPT-IN (tile id 736, or STP_S64=1 in the environment for stp_conv2d's automatic choice
- * when the launch has at least two tiles of 8 x 32 pixels per CU): at the U-Net's batch the halo kernel is as fast (conv_sc.hip has the numbers).
+ * when the launch has at least two tiles of 8 x 32 pixels per CU): at the U-Net's batch the halo kernel is as fast (conv_sc_s64.hip has the numbers).
  * stats_tiles = stp_conv2d_s64_stats_tiles(p) columns (one per workgroup). */
 int stp_conv2d_s64_eligible(const stp_conv_params* p);
 int stp_conv2d_s64_stats_tiles(const stp_conv_params* p);
@@ -268,7 +268,7 @@ int stp_conv2d_wgrad(const stp_wgrad_params* p, void* workspace, size_t workspac
  * of 64 or a power of two >= 16 with Ho * Wo % 64 == 0; STP_E_BADARG otherwise). */
 int stp_conv2d_wgrad_partial(const stp_wgrad_params* p, void* workspace, size_t workspace_bytes, int32_t variant, void* stream);
 int stp_conv2d_wgrad_reduce(const stp_wgrad_params* p, const void* workspace, int32_t variant, void* stream);
-/* Small-channel weight gradient (conv_sc.hip): chosen automatically by variant 0 when eligible. */
+/* Small-channel weight gradient (conv_sc_wgrad.hip): chosen automatically by variant 0 when eligible. */
 int stp_wgrad_sc_eligible(const stp_wgrad_params* p);
 int stp_wgrad_sc_slabs(const stp_wgrad_params* p);
 int stp_wgrad_sc_partial(const stp_wgrad_params* p, void* workspace, void* stream);

@@ -38,6 +38,7 @@
 // Epilogue (bias, residual, ReLU, dual destination, accumulate, BatchNormalization statistics, BatchNormalization-backward
 // sums): conv_common.h, shared with conv_igemm.hip.
 #include "conv_common.h"
+#include "launch.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -932,7 +933,6 @@ static const HaloCfg HALO_CFGS[] = {{16, 128}, {8, 128}, {16, 64}, {8, 64}, {32,
 
 template <int TH, int BM, int WM, int WN, int EP>
 static int launch_halo_ep(ConvArgs& a, hipStream_t s) {
-  static bool attr_set = false;
   constexpr int NHP = (TH + 2) * 18, SROWS = (NHP + 7) / 8 * 8;
   const bool src2 = a.C1 > 0 || a.mode == STP_SRC_NEAREST2X || a.d2s;
   // STP_HALO_RING=6: the 8-row tiles with one source take the six-stage weight ring (experiment switch; default below)
@@ -943,9 +943,7 @@ static int launch_halo_ep(ConvArgs& a, hipStream_t s) {
   if (lds < lds_ep) lds = lds_ep;
   a.ntile_m = ceil_div(a.Cout, BM);
   a.ntile_n = a.N * (a.Ho / TH) * (a.Wo / 16);
-  static bool attr_set_pbn = false, attr_set_src2 = false;
   const bool pbn = a.pbn.mean != nullptr;
-  static bool attr_set_s2d = false, attr_set_fold1 = false;
   const bool fold1 = !a.d2s && a.fold_weight != nullptr;      // (set by stp_conv2d_halo: fold_src / fold_weight / fold_C on a stride-1 launch)
   if (a.d2s) {
     if (pbn || BM != 128 || (EP != 0 && EP != 2)) return STP_E_BADARG;
@@ -962,19 +960,11 @@ static int launch_halo_ep(ConvArgs& a, hipStream_t s) {
   if constexpr (BM == 128 && (EP == 0 || EP == 2)) {
     if (a.d2s) kern = conv_halo_s2d_kernel<TH, BM, WM, WN, EP>;
   }
-  static bool attr_set_r6 = false;
   if constexpr (TH == 8) {
     if (ring6) kern = conv_halo_r6_kernel<TH, BM, WM, WN, EP>;
   }
-  bool& done = ring6 ? attr_set_r6 : a.d2s ? attr_set_s2d : fold1 ? attr_set_fold1 : src2 ? attr_set_src2 : pbn ? attr_set_pbn : attr_set;
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return STP_E_LAUNCH;
-    done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(a.ntile_m * a.ntile_n), dim3(512), lds, s, a);
-  STP_LAUNCH_CHECK();
-  return STP_OK;
+  // (lds varies per launch: whichever kernel was chosen gets the whole CU's 160 KB once)
+  return stp_launch_lds_reserve(kern, 160 * 1024, dim3(a.ntile_m * a.ntile_n), dim3(512), lds, s, a);
 }
 
 template <int TH, int BM, int WM, int WN>
@@ -1020,15 +1010,6 @@ static bool halo_p64_ok(const stp_conv_params* p) {
   return on && p->C0 == 64 && p->C1 == 0 && p->Cout == 64 && p->Cd0 == 64 && !p->dst1 && p->src0_mode == STP_SRC_DIRECT && !p->fold_src && !p->s2d_dgrad &&
          !p->src_bn_mean && !p->dst_sum2x2 && (p->Ho % 8) == 0;
 }
-static int halo_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    n = v;
-  }
-  return n;
-}
 template <int EP>
 static int launch_halo_p64_ep(ConvArgs& a, hipStream_t s) {
   constexpr int TH = 8, NHP = (TH + 2) * 18, SROWS = (NHP + 7) / 8 * 8;
@@ -1037,16 +1018,9 @@ static int launch_halo_p64_ep(ConvArgs& a, hipStream_t s) {
   a.ntile_m = 1;
   a.ntile_n = a.N * (a.Ho / TH) * (a.Wo / 16);
   auto kern = conv_halo_p64_kernel<8, 64, 2, 2, EP>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return STP_E_LAUNCH;
-    attr_set = true;
-  }
-  const int slots = 2 * halo_cus();
+  const int slots = 2 * stp_cu_count();
   const int nwg = a.ntile_n < slots ? a.ntile_n : slots;       // two workgroups per CU walk tile = round * nwg + workgroup
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, a);
-  STP_LAUNCH_CHECK();
-  return STP_OK;
+  return stp_launch_lds_reserve(kern, 160 * 1024, dim3(nwg), dim3(256), lds, s, a);
 }
 static int launch_halo_p64(ConvArgs& a, hipStream_t s) {
   if (a.sum2x2 || a.pbn.mean) return STP_E_BADARG;
@@ -1100,7 +1074,7 @@ static int halo_auto(const stp_conv_params* p) {
     // the weight stream per pixel (scratch/halo_bench.py: 89 -> 81 us); one channel tile: no gain (35 us either way)
     if (p->Cout > 64 && (p->Ho % 32) == 0 && (int64_t)p->N * (p->Ho / 32) * (p->Wo / 16) * ceil_div(p->Cout, 64) >= 512) return 4;
     static const int p64 = getenv("STP_HALO_P64") ? atoi(getenv("STP_HALO_P64")) : 0;      // (experiment: 1 = the persistent form wherever a CU gets two or more tiles)
-    if (p64 == 1 && halo_p64_ok(p) && px8 >= 4 * halo_cus()) return 5;      // (two or more tiles per workgroup)
+    if (p64 == 1 && halo_p64_ok(p) && px8 >= 4 * stp_cu_count()) return 5;      // (two or more tiles per workgroup)
     static const int v4 = getenv("STP_HALO_64V4") ? atoi(getenv("STP_HALO_64V4")) : 0;      // (experiment: 32-row tiles for one channel tile, too)
     if (v4 == 1 && (p->Ho % 32) == 0 && (int64_t)p->N * (p->Ho / 32) * (p->Wo / 16) >= 512) return 4;
     if (px16 * ceil_div(p->Cout, 64) >= 512) return 2;

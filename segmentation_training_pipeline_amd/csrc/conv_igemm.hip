@@ -24,6 +24,7 @@
 //  * conv_igemm_kernel (general): per-lane tap decomposition, global -> VGPR -> ds_write double buffer;
 //    handles the 4-channel stem (C4), 16/32-channel layers and ragged shapes.
 #include "conv_common.h"
+#include "launch.h"
 #include <cstdlib>
 
 // ================================================================================================
@@ -475,44 +476,33 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a) {
 // host side
 // ================================================================================================
 template <typename K>
-static int launch_kernel(K kern, ConvArgs& a, size_t lds, bool& attr_set, hipStream_t s) {
-  if (lds > 64 * 1024 && !attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return STP_E_LAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(a.ntile_m * a.ntile_n), dim3(256), lds, s, a);
-  STP_LAUNCH_CHECK();
-  return STP_OK;
+static int launch_kernel(K kern, ConvArgs& a, size_t lds, hipStream_t s) {
+  return stp_launch_lds(kern, dim3(a.ntile_m * a.ntile_n), dim3(256), lds, s, a);
 }
 
 template <typename T, int BM, int BN, int WM, int WN, bool C4>
 static int launch_gen(ConvArgs& a, hipStream_t s) {
-  static bool attr_set = false;  // one per template instantiation
   a.ntile_m = ceil_div(a.Cout, BM);
   a.ntile_n = ceil_div(a.P, BN);
   a.divNtm = make_fastdiv((uint32_t)a.ntile_m);
-  return launch_kernel(conv_igemm_kernel<T, BM, BN, WM, WN, C4>, a, (size_t)2 * (BM + BN) * 128, attr_set, s);
+  return launch_kernel(conv_igemm_kernel<T, BM, BN, WM, WN, C4>, a, (size_t)2 * (BM + BN) * 128, s);
 }
 
 template <typename T, int BM, int BN, int WM, int WN, int STAGES, bool UNI = true>
 static int launch_ut(ConvArgs& a, hipStream_t s) {
-  static bool attr_set = false;
   a.ntile_m = ceil_div(a.Cout, BM);
   a.ntile_n = ceil_div(a.P, BN);
   a.divNtm = make_fastdiv((uint32_t)a.ntile_m);
   constexpr size_t LDS = (size_t)STAGES * (BM + BN) * 128 + 4096;
   if constexpr (UNI && (STAGES == 2 || (STAGES == 4 && BM == 64 && BN == 64))) {      // (the tiles auto_tile() picks: stp_conv2d sets upc for these only)
-    static bool attr_set_upc = false;
-    if (a.upc) return launch_kernel(conv_igemm_ut_kernel<T, BM, BN, WM, WN, STAGES, UNI, true, true>, a, LDS, attr_set_upc, s);
+    if (a.upc) return launch_kernel(conv_igemm_ut_kernel<T, BM, BN, WM, WN, STAGES, UNI, true, true>, a, LDS, s);
   }
   if (a.upc) return STP_E_BADARG;
   if constexpr (UNI) {
-    static bool attr_set_zp = false;
-    if (a.zperm) return launch_kernel(conv_igemm_ut_kernel<T, BM, BN, WM, WN, STAGES, UNI, false, true>, a, LDS, attr_set_zp, s);
+    if (a.zperm) return launch_kernel(conv_igemm_ut_kernel<T, BM, BN, WM, WN, STAGES, UNI, false, true>, a, LDS, s);
   }
   if (a.zperm) return STP_E_BADARG;
-  return launch_kernel(conv_igemm_ut_kernel<T, BM, BN, WM, WN, STAGES, UNI>, a, LDS, attr_set, s);
+  return launch_kernel(conv_igemm_ut_kernel<T, BM, BN, WM, WN, STAGES, UNI>, a, LDS, s);
 }
 
 // Tile ids (output channels x pixels per workgroup):
@@ -648,10 +638,10 @@ static int halo_variant_for(const stp_conv_params* p) {
   return stp_conv2d_halo_variant(p);
 }
 #define STP_TILE_SC 512  // the small-channel halo-tile kernel of conv_sc.hip
-#define STP_TILE_STEM 768  // the 7x7 / stride-2 stem kernel of conv_sc.hip
-#define STP_TILE_SCW 640  // the wide-output (two-destination, 2x2-summed) data-gradient kernel of conv_sc.hip
-#define STP_TILE_SCN 704  // the narrow-output (upsample + concat -> 32 channels) forward kernel of conv_sc.hip
-#define STP_TILE_S64 736  // the 64 -> 64 channel weights-in-registers kernel of conv_sc.hip (opt-in: STP_S64=1, or this tile id)
+#define STP_TILE_STEM 768  // the 7x7 / stride-2 stem kernel of conv_sc_stem.hip
+#define STP_TILE_SCW 640  // the wide-output (two-destination, 2x2-summed) data-gradient kernel of conv_sc_wide.hip
+#define STP_TILE_SCN 704  // the narrow-output (upsample + concat -> 32 channels) forward kernel of conv_sc_narrow.hip
+#define STP_TILE_S64 736  // the 64 -> 64 channel weights-in-registers kernel of conv_sc_s64.hip (opt-in: STP_S64=1, or this tile id)
 #define STP_TILE_PW 800   // the pointwise (1x1 / stride 1) pixel-streaming kernel of conv_pw.hip (round 6)
 extern "C" int stp_conv2d_pw_eligible(const stp_conv_params* p);
 extern "C" int stp_conv2d_pw_cols(const stp_conv_params* p);

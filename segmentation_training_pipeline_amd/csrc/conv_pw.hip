@@ -325,14 +325,8 @@ extern "C" int stp_conv2d_pw_eligible(const stp_conv_params* p) {
   return 1;
 }
 
-static int pw_cu_count() {
-  int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-    n = 256;   // MI355X (also the answer on a build host without a GPU: plan sizes must not depend on where they are computed)
-  return n;
-}
 static int pw_grid(const PwConfig* c, int64_t P) {
-  static const int cus = pw_cu_count();
+  const int cus = stp_cu_count();
   const int lds = 2 * c->tp * c->cin * 2;
   int per_cu = c->nw == 4 ? 2 : 1;                                     // <= 256 registers per lane: 8 waves per CU
   if (lds * per_cu > 160 * 1024) per_cu = 1;
@@ -350,15 +344,7 @@ extern "C" int stp_conv2d_pw_cols(const stp_conv_params* p) {
 template <int CIN, int COUT, int NW, int TP, int EP, bool OPA, bool OPR>
 static int pw_launch1(const PwArgs& a, int grid, hipStream_t s) {
   constexpr int lds = 2 * TP * CIN * 2;
-  static bool attr_set = false;
-  if (lds > 64 * 1024 && !attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pw_kernel<CIN, COUT, NW, TP, EP, OPA, OPR>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return STP_E_LAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_pw_kernel<CIN, COUT, NW, TP, EP, OPA, OPR>), dim3(grid), dim3(NW * 64), lds, s, a);
-  STP_LAUNCH_CHECK();
-  return STP_OK;
+  return stp_launch_lds(conv_pw_kernel<CIN, COUT, NW, TP, EP, OPA, OPR>, dim3(grid), dim3(NW * 64), lds, s, a);
 }
 
 template <int CIN, int COUT, int NW, int TP>

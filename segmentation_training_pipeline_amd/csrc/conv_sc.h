@@ -1,7 +1,9 @@
-// Shared declarations of the small-channel kernels (conv_sc.hip: generic streaming / single-shot / wide forms; conv_sc_lean.hip: the
-// lean streaming kernel of round 4).
+// Shared declarations of the small-channel kernels: conv_sc.hip (generic forward, single-shot and streaming), conv_sc_wide.hip (scw),
+// conv_sc_narrow.hip (scn), conv_sc_s64.hip (s64), conv_sc_stem.hip (7x7 stem), conv_sc_wgrad.hip (weight gradient) and
+// conv_sc_lean.hip (the lean streaming kernels of round 4).  Device templates shared by some of them: conv_sc_epilogue.h.
 #pragma once
 #include "common.h"
+#include "launch.h"
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -82,18 +84,10 @@ static inline bool sc_stream_on() {
   static const bool on = !(getenv("STP_SC_STREAM") && atoi(getenv("STP_SC_STREAM")) == 0);
   return on;
 }
-static inline int sc_cu_count() {
-  static const int cus = [] {
-    int d = 0, n = 0;
-    if (hipGetDevice(&d) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0) n = 256;
-    return n;      // MI355X (also the answer on a build host without a GPU: plan sizes must not depend on where they are computed)
-  }();
-  return cus;
-}
 // workgroups of the streaming kernel: CUs x the co-resident workgroups its launch bound leaves room for, at most one per tile
 static inline int sc_stream_blocks(int dtype, int cin, int cout, int ntiles) {
   const int per_cu = cout <= 16 ? (dtype == STP_H16 && cin <= 16 ? SC_WPE_SMALL : 3) : 2;
-  const int64_t b = (int64_t)sc_cu_count() * per_cu;
+  const int64_t b = (int64_t)stp_cu_count() * per_cu;
   return (int)(b < ntiles ? b : ntiles);
 }
 

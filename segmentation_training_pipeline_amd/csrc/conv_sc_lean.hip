@@ -442,15 +442,7 @@ static int launch_scl(const ScArgs& a, hipStream_t s) {
   constexpr int NV = (UP ? (SC_TH / 2 + 2) * (SC_TW / 2 + 2) : SC_HH * SC_HW) * (CIN / 8), NPASS = (NV + 255) / 256;
   const size_t lds = (size_t)2 * NPASS * 4096 + (4 * TM * 16 * 2 + 64) * sizeof(float);
   const int blocks = sc_stream_blocks(STP_H16, CIN, TM * 16, ntiles);
-  static bool attr_set = false;
-  if (lds > 64 * 1024 && !attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sc_lean_kernel<CIN, TM, EPI, PBN, UP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return STP_E_LAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_sc_lean_kernel<CIN, TM, EPI, PBN, UP>), dim3(blocks), dim3(256), lds, s, a);
-  STP_LAUNCH_CHECK();
-  return STP_OK;
+  return stp_launch_lds(conv_sc_lean_kernel<CIN, TM, EPI, PBN, UP>, dim3(blocks), dim3(256), lds, s, a);
 }
 
 template <int EPI, bool PBN, bool UP>
@@ -500,7 +492,7 @@ int sc_lean_launch(const ScArgs& a, int cin, int dtype, hipStream_t s) {
 // =================================================================================================
 // LEAN small-channel WEIGHT GRADIENT:  dW[co][tap * CIN + ci] = sum over pixels of dY[p][co] * X[p + tap][ci]
 //
-// conv_sc_wgrad_stream_kernel (conv_sc.hip) gives wave w the taps w, w + 4, w + 8 of every tile row: wave 0 does 3/2 of the others' work,
+// conv_sc_wgrad_stream_kernel (conv_sc_wgrad.hip) gives wave w the taps w, w + 4, w + 8 of every tile row: wave 0 does 3/2 of the others' work,
 // every wave re-reads the dY fragment of every row, the row loop keeps one transpose read in flight, and the compiler puts an
 // s_waitcnt vmcnt(0) - i.e. the NEXT tile's LDS-DMA - in front of the first LDS read of every tile (it cannot tell the two apart).
 // 56-130 us per launch for layers whose operands take 17-34 us at HBM speed.  Here:
@@ -738,15 +730,7 @@ template <int CIN, int COUT, bool PBN, bool UP>
 static int launch_scwl(const ScWgArgs& a, int blocks, hipStream_t s) {
   constexpr int NPX = ((UP ? (SC_TH / 2 + 2) * (SC_TW / 2 + 2) : SC_HH * SC_HW) * (CIN / 8) + 255) / 256, NPD = (SC_TH * SC_TW * (COUT / 8) + 255) / 256;
   const size_t lds = (size_t)2 * (NPX + NPD) * 4096;
-  static bool attr_set = false;
-  if (lds > 64 * 1024 && !attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sc_wgrad_lean_kernel<CIN, COUT, PBN, UP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return STP_E_LAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_sc_wgrad_lean_kernel<CIN, COUT, PBN, UP>), dim3(blocks), dim3(256), lds, s, a);
-  STP_LAUNCH_CHECK();
-  return STP_OK;
+  return stp_launch_lds(conv_sc_wgrad_lean_kernel<CIN, COUT, PBN, UP>, dim3(blocks), dim3(256), lds, s, a);
 }
 
 static bool sc_wg_lean_3232() {
@@ -776,7 +760,7 @@ int sc_wg_lean_launch(const ScWgArgs& a, int cin, int cout, int dtype, int block
 }
 
 // =================================================================================================
-// PERSISTENT form of the stem kernel (7x7 / stride 2 / pad 3, 4 padded input channels -> 64; conv_stem_kernel in conv_sc.hip is the
+// PERSISTENT form of the stem kernel (7x7 / stride 2 / pad 3, 4 padded input channels -> 64; conv_stem_kernel in conv_sc_stem.hip is the
 // single-shot form): there every one of the 4096 workgroups of the headline launch copied the 29 KB weight matrix and its 11.8 KB input
 // patch through registers into LDS, synchronised, multiplied and retired - 79 us for a layer that moves 168 MB (25 us at HBM speed).
 // Here workgroups are persistent (two per CU): the weights go to LDS once per workgroup, the input patch of the NEXT 8 x 32 output
@@ -998,20 +982,12 @@ bool stem_lean_serves(int N, int H, int W) {
   return on && !(W & 1) && (uint64_t)N * H * W * 8 < 0x80000000ull;
 }
 int stem_lean_blocks(int ntiles) {
-  const int64_t b = (int64_t)sc_cu_count() * 2;
+  const int64_t b = (int64_t)stp_cu_count() * 2;
   return (int)(b < ntiles ? b : ntiles);
 }
 int stem_lean_launch(const StemArgs& a, hipStream_t s) {
   if (!stem_lean_serves(a.N, a.H, a.W) || !a.src_bytes) return 1;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_lean_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)STL_LDS) != hipSuccess)
-      return STP_E_LAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(conv_stem_lean_kernel, dim3(stem_lean_blocks(a.N * a.tiles_x * a.tiles_y)), dim3(256), STL_LDS, s, a);
-  STP_LAUNCH_CHECK();
-  return STP_OK;
+  return stp_launch_lds(conv_stem_lean_kernel, dim3(stem_lean_blocks(a.N * a.tiles_x * a.tiles_y)), dim3(256), STL_LDS, s, a);
 }
 
 // =================================================================================================
@@ -1185,7 +1161,7 @@ bool stem_wg_lean_serves(int N, int H, int W, int Ho, int Wo) {
   return on && !(W & 1) && (uint64_t)N * H * W * 8 < 0x80000000ull && (uint64_t)N * Ho * Wo * 128 < 0x80000000ull;
 }
 int stem_wg_lean_blocks(int N, int Ho, int Wo) {
-  const int64_t tiles = (int64_t)N * ((Ho + SWG_TH - 1) / SWG_TH) * ((Wo + SC_TW - 1) / SC_TW), b = (int64_t)sc_cu_count() * 2;
+  const int64_t tiles = (int64_t)N * ((Ho + SWG_TH - 1) / SWG_TH) * ((Wo + SC_TW - 1) / SC_TW), b = (int64_t)stp_cu_count() * 2;
   return (int)(b < tiles ? b : tiles);
 }
 int stem_wg_lean_launch(const void* src, const void* dy, float* slabs, int N, int H, int W, int Ho, int Wo, hipStream_t s) {

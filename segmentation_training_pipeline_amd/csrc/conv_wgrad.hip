@@ -15,6 +15,7 @@
 // zero-insert / concat folded in).  Pixels are partitioned over `splits` slabs (split-K) that
 // a second kernel sums in fixed order: deterministic, no atomics.
 #include "common.h"
+#include "launch.h"
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -1485,14 +1486,7 @@ struct WgradPlan {
 extern "C" int stp_wgrad_sc_eligible(const stp_wgrad_params* p);
 extern "C" int stp_wgrad_sc_slabs(const stp_wgrad_params* p);
 extern "C" int stp_wgrad_sc_partial(const stp_wgrad_params* p, void* workspace, void* stream);
-#define WG_TILE_SC 100  // small-channel halo-tile kernel (conv_sc.hip): splits = number of persistent workgroups
-
-static int device_cu_count() {
-  int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-    n = 256;   // MI355X (also the answer on a build host without a GPU: plan sizes must not depend on where they are computed)
-  return n;
-}
+#define WG_TILE_SC 100  // small-channel halo-tile kernel (conv_sc_wgrad.hip): splits = number of persistent workgroups
 
 static WgradPlan plan_wgrad(const stp_wgrad_params* p) {
   WgradPlan w;
@@ -1518,7 +1512,7 @@ static WgradPlan plan_wgrad(const stp_wgrad_params* p) {
     // 3 for 64x128), splits = floor(slots / tiles).  One workgroup more than the slots costs a whole extra round
     // (scratch/wgrad_split_sweep.py: 128->128 @64x64, 9 tiles: 57 splits = 513 workgroups 49 us, 56 splits = 504 workgroups 33 us);
     // every split also costs a slab write + read of Cout*K floats, so fewer is better at equal fill.
-    static const int cus = device_cu_count();
+    const int cus = stp_cu_count();
     static const int target = getenv("STP_WGRAD_BLOCKS") ? atoi(getenv("STP_WGRAD_BLOCKS")) : 0;
     const int slots = target > 0 ? target : cus * (w.bm == 64 ? 3 : 2);
     splits = slots / tiles;
@@ -1565,7 +1559,7 @@ static WgradPlan plan_wgrad_row(const stp_wgrad_params* p) {
   const int tiles = w.ntile_m * w.ntile_n;
   int splits = p->splits;
   if (splits <= 0) {
-    static const int cus = device_cu_count();
+    const int cus = stp_cu_count();
     static const int target = getenv("STP_WGRAD_ROW_BLOCKS") ? atoi(getenv("STP_WGRAD_ROW_BLOCKS")) : 0;
     const int slots = target > 0 ? target : cus * (w.bm == 64 ? 3 : 2);   // co-resident workgroups (LDS: 40 / 56 KB each)
     splits = slots / tiles;
@@ -1597,32 +1591,22 @@ extern "C" size_t stp_conv2d_wgrad_workspace_bytes(const stp_wgrad_params* p) {
 }
 
 template <typename K>
-static int launch_wg(K kern, WgradArgs& a, size_t lds, int splits, bool& attr_set, hipStream_t s) {
-  if (lds > 64 * 1024 && !attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return STP_E_LAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(a.ntile_m * a.ntile_n * splits), dim3(256), lds, s, a);
-  STP_LAUNCH_CHECK();
-  return STP_OK;
+static int launch_wg(K kern, WgradArgs& a, size_t lds, int splits, hipStream_t s) {
+  return stp_launch_lds(kern, dim3(a.ntile_m * a.ntile_n * splits), dim3(256), lds, s, a);
 }
 
 template <typename T, int BM, int BN, int WM, int WN, bool C4>
 static int launch_wgrad(WgradArgs& a, int splits, hipStream_t s) {
-  static bool attr_set = false;
   constexpr int PK = 128 / (int)sizeof(T);
-  return launch_wg(conv_wgrad_kernel<T, BM, BN, WM, WN, C4>, a, (size_t)2 * PK * (BM + BN) * sizeof(T), splits, attr_set, s);
+  return launch_wg(conv_wgrad_kernel<T, BM, BN, WM, WN, C4>, a, (size_t)2 * PK * (BM + BN) * sizeof(T), splits, s);
 }
 
 template <typename T, int BM, int BN, int WM, int WN, int STAGES>
 static int launch_wgrad_dma(WgradArgs& a, int splits, hipStream_t s) {
-  static bool attr_set = false;
   constexpr int PK = 128 / (int)sizeof(T);
-  static bool attr_set_u = false;
   const size_t lds = (size_t)STAGES * PK * (BM + BN) * sizeof(T) + 4096;
-  if (a.rowu) return launch_wg(conv_wgrad_dma_kernel<T, BM, BN, WM, WN, STAGES, true>, a, lds, splits, attr_set_u, s);
-  return launch_wg(conv_wgrad_dma_kernel<T, BM, BN, WM, WN, STAGES, false>, a, lds, splits, attr_set, s);
+  if (a.rowu) return launch_wg(conv_wgrad_dma_kernel<T, BM, BN, WM, WN, STAGES, true>, a, lds, splits, s);
+  return launch_wg(conv_wgrad_dma_kernel<T, BM, BN, WM, WN, STAGES, false>, a, lds, splits, s);
 }
 
 // variant: 0 = auto, 1 = legacy register-staged, 2/3 = DMA ring with that many stages
@@ -1752,7 +1736,7 @@ struct WgGroupPlan {
 };
 
 static int wg_group_slots(int bm, bool taps9) {
-  static const int cus = device_cu_count();
+  const int cus = stp_cu_count();
   static const int target = getenv("STP_WGRAD_GROUP_SLOTS") ? atoi(getenv("STP_WGRAD_GROUP_SLOTS")) : 0;
   if (target > 0) return target;
   if (taps9) return cus;                                 // 512 threads, 120-144 KB of LDS: one workgroup per CU
@@ -1928,51 +1912,20 @@ extern "C" int stp_wgrad_group_partial(const void* host_table, const void* dev_t
   if (hd->taps9) {
     // 3 stages x (dY tile + 256 halo rows of 128 bytes - the seg = 64 geometry, the largest)
     const size_t lds9 = (size_t)3 * ((hd->bm == 128 ? 16384 : 8192) + 256 * 128);
-    static bool a128 = false, a64 = false, a32 = false;
-#define STP_GROUP9_LAUNCH(BM_, FLAG_)                                                                                               \
-  do {                                                                                                                              \
-    auto kern = conv_wgrad_taps9_group_kernel<BM_, 3>;                                                                              \
-    if (!FLAG_) {                                                                                                                   \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds9) != hipSuccess) \
-        return STP_E_LAUNCH;                                                                                                        \
-      FLAG_ = true;                                                                                                                 \
-    }                                                                                                                               \
-    hipLaunchKernelGGL(kern, dim3(hd->n_wg), dim3(512), lds9, s, (const char*)dev_table, (f32x4*)workspace);                        \
-  } while (0)
-    if (hd->bm == 128 && hd->taps9 == 2) {
-      static bool a128m = false;
-      auto kern = conv_wgrad_taps9_group_kernel<128, 3, true>;
-      if (!a128m) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds9) != hipSuccess) return STP_E_LAUNCH;
-        a128m = true;
-      }
-      hipLaunchKernelGGL(kern, dim3(hd->n_wg), dim3(512), lds9, s, (const char*)dev_table, (f32x4*)workspace);
-    } else if (hd->bm == 128) STP_GROUP9_LAUNCH(128, a128);
-    else if (hd->bm == 64) STP_GROUP9_LAUNCH(64, a64);
-    else STP_GROUP9_LAUNCH(32, a32);
-#undef STP_GROUP9_LAUNCH
-    STP_LAUNCH_CHECK();
-    return STP_OK;
+    static_assert((size_t)3 * (8192 + 256 * 128) > STP_LDS_DEFAULT, "every launch of these kernels needs the grant");
+    auto launch9 = [&](auto kern) { return stp_launch_lds(kern, dim3(hd->n_wg), dim3(512), lds9, s, (const char*)dev_table, (f32x4*)workspace); };
+    if (hd->bm == 128 && hd->taps9 == 2) return launch9(conv_wgrad_taps9_group_kernel<128, 3, true>);
+    if (hd->bm == 128) return launch9(conv_wgrad_taps9_group_kernel<128, 3>);
+    if (hd->bm == 64) return launch9(conv_wgrad_taps9_group_kernel<64, 3>);
+    return launch9(conv_wgrad_taps9_group_kernel<32, 3>);
   }
   const size_t lds = (size_t)3 * (64 * hd->bm * 2 + 72 * 128);
-  static bool attr128 = false, attr64 = false, attr32 = false, attr128p = false, attr64p = false, attr32p = false;
-#define STP_GROUP_LAUNCH(BM_, WM_, WN_, FLAG_)                                                                                      \
-  do {                                                                                                                              \
-    auto kern = hd->pbn ? conv_wgrad_row_group_pbn_kernel<BM_, WM_, WN_, 3> : conv_wgrad_row_group_kernel<BM_, WM_, WN_, 3>;        \
-    bool& done = hd->pbn ? FLAG_##p : FLAG_;                                                                                        \
-    if (lds > 64 * 1024 && !done) {                                                                                                 \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-        return STP_E_LAUNCH;                                                                                                        \
-      done = true;                                                                                                                  \
-    }                                                                                                                               \
-    hipLaunchKernelGGL(kern, dim3(hd->n_wg), dim3(256), lds, s, (const char*)dev_table, (f32x4*)workspace);                         \
-  } while (0)
-  if (hd->bm == 128) STP_GROUP_LAUNCH(128, 2, 2, attr128);
-  else if (hd->bm == 64) STP_GROUP_LAUNCH(64, 1, 4, attr64);
-  else STP_GROUP_LAUNCH(32, 1, 4, attr32);
-#undef STP_GROUP_LAUNCH
-  STP_LAUNCH_CHECK();
-  return STP_OK;
+  auto launch = [&](auto kern, auto kern_pbn) {
+    return stp_launch_lds(hd->pbn ? kern_pbn : kern, dim3(hd->n_wg), dim3(256), lds, s, (const char*)dev_table, (f32x4*)workspace);
+  };
+  if (hd->bm == 128) return launch(conv_wgrad_row_group_kernel<128, 2, 2, 3>, conv_wgrad_row_group_pbn_kernel<128, 2, 2, 3>);
+  if (hd->bm == 64) return launch(conv_wgrad_row_group_kernel<64, 1, 4, 3>, conv_wgrad_row_group_pbn_kernel<64, 1, 4, 3>);
+  return launch(conv_wgrad_row_group_kernel<32, 1, 4, 3>, conv_wgrad_row_group_pbn_kernel<32, 1, 4, 3>);
 }
 
 extern "C" int stp_wgrad_group_reduce(const void* host_table, const void* dev_table, const void* workspace, void* stream) {
@@ -2040,19 +1993,17 @@ extern "C" int stp_conv2d_wgrad_partial(const stp_wgrad_params* p, void* workspa
     a.xcd = w.ntile_m == 1;
     static const int stages = getenv("STP_WGRAD_ROW_STAGES") ? atoi(getenv("STP_WGRAD_ROW_STAGES")) : 3;
     const size_t lds = (size_t)(stages == 2 ? 2 : 3) * (64 * w.bm * 2 + 72 * 128);    // 25 / 17 KB per stage
-    static bool attr128 = false, attr64 = false, attr_dummy = true;
     if (stages == 2) {
       if (a.pbn.mean) return STP_E_BADARG;       // (the 2-stage what-if build has no fused producer BatchNormalization)
-      if (w.tile == WG_TILE_ROW128) return launch_wg(conv_wgrad_row_kernel<128, 2, 2, 2>, a, lds, w.splits, attr_dummy, s);
-      return launch_wg(conv_wgrad_row_kernel<64, 1, 4, 2>, a, lds, w.splits, attr_dummy, s);
+      if (w.tile == WG_TILE_ROW128) return launch_wg(conv_wgrad_row_kernel<128, 2, 2, 2>, a, lds, w.splits, s);
+      return launch_wg(conv_wgrad_row_kernel<64, 1, 4, 2>, a, lds, w.splits, s);
     }
     if (a.pbn.mean) {      // fused producer BatchNormalization: its own instances
-      static bool attr128p = false, attr64p = false;
-      if (w.tile == WG_TILE_ROW128) return launch_wg(conv_wgrad_row_pbn_kernel<128, 2, 2, 3>, a, lds, w.splits, attr128p, s);
-      return launch_wg(conv_wgrad_row_pbn_kernel<64, 1, 4, 3>, a, lds, w.splits, attr64p, s);
+      if (w.tile == WG_TILE_ROW128) return launch_wg(conv_wgrad_row_pbn_kernel<128, 2, 2, 3>, a, lds, w.splits, s);
+      return launch_wg(conv_wgrad_row_pbn_kernel<64, 1, 4, 3>, a, lds, w.splits, s);
     }
-    if (w.tile == WG_TILE_ROW128) return launch_wg(conv_wgrad_row_kernel<128, 2, 2, 3>, a, lds, w.splits, attr128, s);
-    return launch_wg(conv_wgrad_row_kernel<64, 1, 4, 3>, a, lds, w.splits, attr64, s);
+    if (w.tile == WG_TILE_ROW128) return launch_wg(conv_wgrad_row_kernel<128, 2, 2, 3>, a, lds, w.splits, s);
+    return launch_wg(conv_wgrad_row_kernel<64, 1, 4, 3>, a, lds, w.splits, s);
   }
   if (p->dtype == STP_H16)
     return c4 ? launch_wgrad_tile<bf16_t, true>(a, w, dma, variant, s) : launch_wgrad_tile<bf16_t, false>(a, w, dma, variant, s);

@@ -2,6 +2,7 @@
 // (both can complete a BatchNormalization backward), FPN's upsample-and-add, bilinear resize by an integer factor with its family of
 // gradient kernels, the sum of resized pyramid levels (PSPNet head) and nearest resize.
 #include "stream_ops.h"
+#include "launch.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -900,18 +901,10 @@ extern "C" int stp_resize_bilinear_bwd(const void* dy, void* dx, int32_t N, int3
     const size_t lds = (size_t)2 * cols * CC * sizeof(float);
     if (tile_on && V == 8 && factor >= 2 && C >= 32 && C % CC == 0 && cols * (CC / 8) <= 256 * RBT_K && lds <= 96 * 1024 &&
         (int64_t)N * ((H + 1) / 2) <= 65535 && C / CC <= 65535 && !(reinterpret_cast<uintptr_t>(dy) & 15) && !(reinterpret_cast<uintptr_t>(dx) & 7)) {
-      static bool attr_set = false;
-      if (lds > 64 * 1024 && !attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(resize_bilinear_bwd_tile_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                96 * 1024) != hipSuccess)
-          return STP_E_LAUNCH;
-        attr_set = true;
-      }
       const dim3 grid((unsigned)ceil_div(W, WS), (unsigned)(N * ((H + 1) / 2)), (unsigned)(C / CC));
-      hipLaunchKernelGGL(resize_bilinear_bwd_tile_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)dy, (bf16_t*)dx, H, W, C,
-                         factor, ldo, coff, accumulate, WS, CC);
-      STP_LAUNCH_CHECK();
-      return STP_OK;
+      // (cols * (CC / 8) <= 256 * RBT_K bounds lds by 48 KB today; a larger RBT_K gets its grant from the helper)
+      return stp_launch_lds(resize_bilinear_bwd_tile_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)dy, (bf16_t*)dx, H, W, C,
+                            factor, ldo, coff, accumulate, WS, CC);
     }
   }
   if (V > 1 && factor >= 2) {

@@ -372,7 +372,7 @@ class Plan(object):
     def _fuse_bn_into_consumers(self):
         """BatchNormalization(+activation) outputs that only convolutions with a fused-producer path read:
 
-        * every consumer is a small-channel convolution (conv_sc.hip: forward AND weight gradient normalise the pre-BN tensor
+        * every consumer is a small-channel convolution (conv_sc.hip / conv_sc_wgrad.hip: forward AND weight gradient normalise the pre-BN tensor
           while staging it): the stp_bn_apply launch is dropped; ``tensor(name)`` still materialises the tensor on demand;
         * some consumers are halo-kernel convolutions (conv_halo.hip: the forward normalises the slab in LDS): when every one of
           their weight gradients runs on the row-of-taps kernel (conv_wgrad.hip normalises its halo tile the same way) the launch

@@ -1,5 +1,5 @@
 """Float64 numpy restatement of the convolution weight gradient (csrc/conv_wgrad.hip, the small-channel and stem kernels of
-conv_sc.hip / conv_sc_lean.hip), shared by tests/test_wgrad_reference_host.py and tests/test_wgrad_ops_gpu.py.  Not collected, calls no
+conv_sc_wgrad.hip / conv_sc_lean.hip), shared by tests/test_wgrad_reference_host.py and tests/test_wgrad_ops_gpu.py.  Not collected, calls no
 kernel, no torch, no autograd: it is written from the index formula of include/stp_hip.h,
 
     dW[co][(kh * KW + kw) * (C0 + C1) + c] = sum_{n,ho,wo} dY[n,ho,wo,co] * V[n, ho * stride - pad + kh, wo * stride - pad + kw, c]
@@ -209,7 +209,7 @@ def row_eligible(case, dtype):
 
 
 def sc_eligible(case, dtype):
-    """stp_wgrad_sc_eligible of conv_sc.hip restated: the 3x3 small-channel kernel, or the lean stem kernel (even width, 16-bit)."""
+    """stp_wgrad_sc_eligible of conv_sc_wgrad.hip restated: the 3x3 small-channel kernel, or the lean stem kernel (even width, 16-bit)."""
     if case.stem:
         return dtype != "fp32" and case.w % 2 == 0
     vec = 4 if dtype == "fp32" else 8

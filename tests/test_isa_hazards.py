@@ -2,7 +2,7 @@
 that covers it.  The compiler guarantees this for its own reads; the small-channel kernels issue theirs from inline asm (a ring of
 ds_read_b128 kept in flight ahead of the MFMAs, released one by one with counted waits: conv_sc.hip, conv_sc_lean.hip) and declare the ring
 registers as plain outputs - nothing in the language stops a future compiler from copying or spilling such a register between the issue
-and its wait (advisor finding, round 4).  This test compiles the two files to gfx950 assembly and walks every kernel with the LGKM
+and its wait (advisor finding, round 4).  This test compiles the family's files to gfx950 assembly and walks every kernel with the LGKM
 counter's in-order model (LDS operations return in order; lgkmcnt(N) = at most N outstanding)."""
 import os
 import re
@@ -65,17 +65,25 @@ def scan(asm):
     return nk, nreads, bad
 
 
-@pytest.mark.parametrize("src", ["conv_sc_lean.hip", "conv_sc.hip", "conv_pw.hip"])
+# the files of the small-channel family other than conv_sc_lean.hip are one case: the guard on the counts holds for the group's totals
+SC_FAMILY = ("conv_sc.hip", "conv_sc_wide.hip", "conv_sc_narrow.hip", "conv_sc_s64.hip", "conv_sc_stem.hip", "conv_sc_wgrad.hip")
+
+
+@pytest.mark.parametrize("src", ["conv_sc_lean.hip", pytest.param(SC_FAMILY, id="conv_sc_family"), "conv_pw.hip"])
 def test_async_lds_reads_are_not_touched_before_their_wait(src, tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    out = str(tmp_path / (src + ".s"))
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=on", "-Wno-unused-result", "--cuda-device-only", "-S",
-                        os.path.join(CSRC, src), "-o", out], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    with open(out) as f:
-        nk, nreads, bad = scan(f.read())
+    nk, nreads, bad = 0, 0, []
+    for name in ((src,) if isinstance(src, str) else src):
+        out = str(tmp_path / (name + ".s"))
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=on", "-Wno-unused-result", "--cuda-device-only", "-S",
+                            os.path.join(CSRC, name), "-o", out], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        with open(out) as f:
+            k, n, b = scan(f.read())
+        assert k >= 1, (name, k)                                # every file of a group holds a kernel
+        nk, nreads, bad = nk + k, nreads + n, bad + b
     assert nk >= 4 and nreads > 200, (nk, nreads)              # the walk saw the kernels and their LDS reads
     assert not bad, "registers of an LDS read in flight are touched before its wait:\n" + "\n".join(
         "%s line %d: %s (v%s)" % (k, ln, ins, regs) for k, ln, ins, regs in bad[:20])
