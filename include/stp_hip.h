@@ -548,8 +548,8 @@ int stp_softmax_cce_dice(const void* logits, const uint8_t* target, int64_t pixe
  * term's per-class logarithms are then not evaluated), the rest as
  * stp_softmax_cce_dice.  dlogits [pixels][dl_channels] gets the classes gradients x grad_scale and exactly-zero padding (NULL: scalars
  * only).  Deterministic (fixed-order reduction, no atomics).  STP_E_BADARG for classes outside 2..32, ldc < classes, dl_channels <
- * classes or the other build's 16-bit dtype; STP_E_WORKSPACE below stp_loss_workspace_bytes().  Not here: lovasz_loss on several
- * classes, a fused low-resolution (_up) form, a bias-gradient shortcut from workgroup sums. */
+ * classes or the other build's 16-bit dtype; STP_E_WORKSPACE below stp_loss_workspace_bytes().  Not here: a fused low-resolution
+ * (_up) form, a bias-gradient shortcut from workgroup sums.  (The Lovasz term of several classes: stp_lovasz_softmax, below.) */
 int stp_softmax_loss_ex(const void* logits, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc,
                         int32_t dtype, const float* weights5, float* scalars, void* dlogits, int32_t dl_channels,
                         float grad_scale, void* workspace, size_t workspace_bytes, void* stream);
@@ -574,11 +574,41 @@ int stp_softmax_loss_ex(const void* logits, const uint8_t* target, int64_t pixel
  * scalars (fp32[14]): [0..11] as stp_softmax_loss_ex ([11] = 0 when focal_loss has no weight), [12] = n, [13] = sum_i omega_i (n is exact
  * in its float up to 2^24 counted pixels; the gradient pass reads it from there).  Deterministic: fixed-order reduction, no atomics.
  * STP_E_BADARG as stp_softmax_loss_ex, and for ignore_label outside -1..255; STP_E_WORKSPACE below stp_loss_workspace_bytes().
- * Not here: a fused low-resolution (_up) form, class weights on dice_loss / iou_loss, lovasz_loss. */
+ * Not here: a fused low-resolution (_up) form, class weights on dice_loss / iou_loss. */
 int stp_softmax_loss_masked(const void* logits, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc,
                             int32_t dtype, const float* weights5, float* scalars, void* dlogits, int32_t dl_channels,
                             float grad_scale, void* workspace, size_t workspace_bytes, int32_t ignore_label,
                             const float* class_weights, void* stream);
+/* lovasz_softmax: the Lovasz-Softmax of Berman et al. (the mean-IoU surrogate) on the multi-class head, batch form (per_image=False,
+ * classes='present').  Runs AFTER stp_softmax_loss_ex / stp_softmax_loss_masked on the same logits, scalars (fp32[16]) and dlogits and ADDS
+ * its term, as stp_lovasz_hinge does for one class.  The arithmetic, fixed HERE (the reference pins none):
+ *   p = softmax(z) in fp32 over the first `classes` channels; t_i the stored target, v_i = [t_i != ignore_label] (-1: every pixel counts);
+ *   the class of a counted pixel is min(t_i, classes - 1), y_ic its one-hot target.  For each class c over the counted pixels of the batch:
+ *     e_ic = y_ic ? 1 - p_ic : p_ic;  G_c = sum_i v_i y_ic, the class is present iff G_c > 0;
+ *     the errors ordered by descending e, ties by ascending pixel index (a stable sort of class-major keys);
+ *     at 0-based rank r, c1_r / c0_r = positives / negatives among ranks 0..r;  g_r = 1 / (G + c0_r) for a positive,
+ *     (G - c1_r) / ((G + c0_r - 1) (G + c0_r)) for a negative (the closed form of the Jaccard increments: sum_r g_r = 1);
+ *     loss_c = sum_r e_(r) g_r.
+ *   lovasz_softmax = (1 / P) sum over the present classes of loss_c, P = their number; P == 0 (nothing counted): the term is 0, every
+ *   gradient element is 0, nothing is NaN.  Class weights do not enter (as they do not enter dice_loss / iou_loss).
+ *   Gradient with g held constant (the surrogate's sub-gradient): d_ic = (y_ic ? -1 : +1) g_rank(i,c) / P for counted pixels of present
+ *   classes, else 0;  dz_ik = p_ik (d_ik - sum_c p_ic d_ic).
+ *   scalars[14] = lovasz_softmax;  scalars[0] += weight * lovasz_softmax (two roundings);  dlogits[i][k] += weight * grad_scale * dz_ik, the
+ *   add made in the storage type; rows of ignored pixels and padding channels are not touched (they stay exactly 0).  dlogits NULL: scalars only.
+ * Launches: key pass, one chip-wide stable radix sort of (class << 30 | reversed error bits, pixel << 1 | y) pairs (rocPRIM through hipCUB),
+ * two scan launches over a grid of (chunk of STP_LOVASZ_SOFTMAX_CHUNK ranks, class) workgroups, a one-workgroup finalize in double, the
+ * gradient pass.  Deterministic (fixed-order sums; the only atomics are integer counts), no allocation, no synchronisation: it captures into
+ * a hipGraph.  workspace: 16-byte aligned, >= stp_lovasz_softmax_workspace_bytes(pixels, classes) (0 = not available: bad sizes, or no device
+ * to size the sort on) - 24 bytes per (pixel, class) for the double-buffered pairs (the coefficient buffer of the gradient lives in the pair
+ * buffer the sort leaves free) plus the sort's temporary storage and two words per (chunk, class).
+ * STP_E_BADARG before any launch: classes outside 2..32, ldc < classes, dl_channels < classes (with dlogits), pixels <= 0 or pixels * classes >=
+ * 2^31, ignore_label outside -1..255, a NULL pointer, the other build's 16-bit dtype; STP_E_WORKSPACE below the queried size.
+ * Not here: a per-image variant, class weights on this term, a low-resolution (_up) form. */
+#define STP_LOVASZ_SOFTMAX_CHUNK 4096 /* ranks of a class segment one scan workgroup walks */
+size_t stp_lovasz_softmax_workspace_bytes(int64_t pixels, int32_t classes);
+int stp_lovasz_softmax(const void* logits, const uint8_t* target, int64_t pixels, int32_t classes, int32_t ldc, int32_t dtype, float weight,
+                       float* scalars, void* dlogits, int32_t dl_channels, float grad_scale, int32_t ignore_label, void* workspace,
+                       size_t workspace_bytes, void* stream);
 /* The same loss on class logits the network produces at 1 / factor of the mask's resolution and resizes bilinearly (segmentation_models
  * 0.2.1: PSPNet `final_interpolation: bilinear` x downsample_factor, schemas/segmentation.raml:225-249; FPN's last UpSampling2D(4,
  * 'bilinear')) - replaces, in the training step, stp_resize_bilinear of the logits + stp_softmax_cce_dice + stp_scale_by_device +

@@ -28,6 +28,7 @@ custom_objects = {
     "categorical_crossentropy": "categorical_crossentropy", "binary_accuracy": "binary_accuracy",
     "iou_loss": "iou_loss", "jaccard_loss": "jaccard_loss", "focal_loss": "focal_loss",        # sigmoid head (stp_sigmoid_loss_ex)
     "lovasz_loss": "lovasz_loss",                                                                # sigmoid head (stp_lovasz_hinge)
+    "lovasz_softmax": "lovasz_softmax",                                                          # softmax heads (stp_lovasz_softmax)
 }
 unsupported_objects = ()
 

@@ -14,6 +14,7 @@ LIB_F16_PATH = os.environ.get("STP_LIB_F16") or os.path.join(HERE, "libstp_hip_f
 
 F32, BF16, U8, F16 = 0, 1, 2, 3
 SRC_DIRECT, SRC_NEAREST2X, SRC_ZEROINS2X = 0, 1, 2
+LOVASZ_SOFTMAX_CHUNK = 4096      # STP_LOVASZ_SOFTMAX_CHUNK of include/stp_hip.h: ranks of a class segment one scan workgroup walks
 
 vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 
@@ -159,6 +160,8 @@ SIGNATURES = {
     "stp_softmax_loss_masked": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, i32, f32, vp, sz, i32, vp, vp]),
     "stp_lovasz_workspace_bytes": (sz, [i64, i32]),
     "stp_lovasz_hinge": (i32, [vp, vp, i32, i64, i32, f32, vp, vp, i32, vp, sz, vp]),
+    "stp_lovasz_softmax_workspace_bytes": (sz, [i64, i32]),
+    "stp_lovasz_softmax": (i32, [vp, vp, i64, i32, i32, i32, f32, vp, vp, i32, f32, i32, vp, sz, vp]),
     "stp_sigmoid": (i32, [vp, vp, i64, i32, vp]),
     "stp_softmax_cce_dice": (i32, [vp, vp, i64, i32, i32, i32, f32, f32, vp, vp, i32, f32, vp, sz, vp]),
     "stp_softmax_cce_dice_up_ok": (i32, [i32, i32, i32]),

@@ -25,6 +25,7 @@ SCALAR_NAMES = ("loss", "binary_crossentropy", "dice_loss", "dice", "binary_accu
 EXTENDED_LOSSES = ("iou_loss", "jaccard_loss", "focal_loss", "lovasz_loss")      # stp_sigmoid_loss_ex + stp_lovasz_hinge (one class);
                                                                                 # stp_sigmoid_multilabel_loss and stp_softmax_loss_ex (several
                                                                                 # classes): all but lovasz_loss
+LOVASZ_SOFTMAX = "lovasz_softmax"    # the Lovasz-Softmax of the softmax heads (stp_lovasz_softmax): its weight rides behind the registry's six
 MAX_MULTILABEL_CLASSES = 8          # one target byte per pixel: bit c = class c
 
 
@@ -39,7 +40,9 @@ def parse_loss(spec, classes=1, architecture=None, activation=None):
     Every head but DeepLabV3's takes them (several classes: the head has to be named - ``activation`` "sigmoid" or "softmax";
     a call that leaves it out gets the two terms every multi-class head has); ``lovasz_loss`` needs the one-class head.
     The cross-entropy term is ``binary_crossentropy`` for the sigmoid heads (one class, or ``activation="sigmoid"`` with several:
-    multi-label) and ``categorical_crossentropy`` for the softmax head (schemas/segmentation.raml:12-21)."""
+    multi-label) and ``categorical_crossentropy`` for the softmax head (schemas/segmentation.raml:12-21).
+    A spec that names ``lovasz_softmax`` (softmax heads of 2..32 classes but DeepLabV3's) returns seven weights: the six above
+    (``w_lovasz`` = 0) and the term's own; every other spec returns what it always did."""
     sigmoid = classes == 1 or is_multilabel(classes, activation)
     ce = "binary_crossentropy" if sigmoid else "categorical_crossentropy"
     w = {ce: 0.0, "dice_loss": 0.0}
@@ -52,15 +55,37 @@ def parse_loss(spec, classes=1, architecture=None, activation=None):
             k, name = float(k), name.strip()
         else:
             k, name = 1.0, term
+        if name == LOVASZ_SOFTMAX:
+            _check_lovasz_softmax(classes, architecture, activation)
+            w.setdefault(name, 0.0)
         if name not in w:
             raise ValueError("loss %r is not available in the HIP backend (have: %s)" % (name, ", ".join(sorted(w))))
         w[name] += k
     if classes > 1 and w.get("lovasz_loss"):
         raise ValueError("lovasz_loss is not available for a multi-label head or a softmax head of several classes "
                          "(the HIP backend has the binary Lovasz hinge of one class)")
+    if w.get(LOVASZ_SOFTMAX):
+        return (w[ce], w["dice_loss"]) + tuple(w[k] for k in EXTENDED_LOSSES) + (w[LOVASZ_SOFTMAX],)
     if any(w.get(k) for k in EXTENDED_LOSSES):
         return (w[ce], w["dice_loss"]) + tuple(w[k] for k in EXTENDED_LOSSES)
     return w[ce], w["dice_loss"]
+
+
+def _check_lovasz_softmax(classes, architecture, activation):
+    """``lovasz_softmax`` needs a softmax head of 2..32 classes on Unet, Linknet, FPN or PSPNet; ValueError says what to use instead."""
+    if classes == 1:
+        raise ValueError("lovasz_softmax needs a softmax head of 2..32 classes; for a one-class sigmoid head use lovasz_loss "
+                         "(the binary Lovasz hinge)")
+    if activation != "softmax":
+        raise ValueError("lovasz_softmax is not available for a multi-label sigmoid head (its classes are not exclusive): use "
+                         "activation: softmax with a label-map mask, or one of binary_crossentropy, dice_loss, iou_loss, jaccard_loss, focal_loss")
+    if architecture == "DeepLabV3":
+        raise ValueError("lovasz_softmax is not available for DeepLabV3 (its loss runs on probabilities): use Unet, Linknet, FPN or PSPNet")
+
+
+def lovasz_softmax_weight(loss_w):
+    """The weight of ``lovasz_softmax`` in what parse_loss returned (0.0 for a spec that does not name it)."""
+    return float(loss_w[6]) if len(loss_w) > 6 else 0.0
 
 
 CLASS_METRICS = ("categorical_accuracy", "mean_iou")      # + iou_class_0 .. iou_class_<classes - 1>: the softmax heads' confusion metrics
@@ -165,6 +190,9 @@ class HipSegModel(object):
         # terms the loss kernel does not evaluate, left out of metrics() and of the epoch log: stp_softmax_loss_ex skips focal_loss'
         # per-class logarithms when the spec gives it no weight (its scalar slot is then 0, not the loss)
         self.unevaluated_terms = ("focal_loss",) if (self.head_activation == "softmax" and len(self.loss_w) > 2 and not self.loss_w[4]) else ()
+        # and the terms a further launch evaluates because the spec gives them a weight, logged on top (pipeline.derived_metrics ``logged``)
+        self.w_lovasz_softmax = lovasz_softmax_weight(self.loss_w)
+        self.evaluated_terms = (LOVASZ_SOFTMAX,) if self.w_lovasz_softmax else ()
         self.optimizer = optimizer.lower()
         if self.optimizer not in ("adam", "sgd", "rmsprop", "nadam"):
             raise ValueError("optimizer %r is not available in the HIP backend (have: SGD, Adam, RMSprop, Nadam)" % optimizer)
@@ -184,7 +212,8 @@ class HipSegModel(object):
         # carries 1/loss_scale (times the data-parallel mean and the clipnorm factor).  2^14 keeps the 1/(N*H*W) BCE gradient
         # of a 16x512x512 batch (2.4e-7, below fp16's normal range) at 4e-3.  The losses without a grad_scale argument (on
         # probabilities: DeepLabV3; lovasz) run unscaled.
-        scalable = architecture != "DeepLabV3" and not (len(self.loss_w) == 6 and self.loss_w[5])      # (.., w_lovasz)
+        # (lovasz_softmax, the seventh weight, has a scaled form: stp_lovasz_softmax takes grad_scale)
+        scalable = architecture != "DeepLabV3" and not (len(self.loss_w) >= 6 and self.loss_w[5])      # (.., w_lovasz, ..)
         if loss_scale is None:
             loss_scale = 16384.0 if (dtype == "fp16" and scalable) else 1.0
             if dtype == "fp16" and not scalable:
@@ -196,6 +225,7 @@ class HipSegModel(object):
             raise ValueError("loss_scale must be positive")
         self.plan.loss_scale = self.loss_scale
         self.plan.masked_loss = self._masked_loss()
+        self.plan.lovasz_softmax = self.w_lovasz_softmax
         # DYNAMIC re-scaling on top of the static scale (fp16 only; STP_DYNAMIC_LOSS_SCALE=0 keeps the static scale + skip-on-overflow of
         # round 3): a device multiplier m (float[8] record, include/stp_hip.h) applied to the loss gradient right after the loss kernel,
         # halved when a step is skipped, doubled after `interval` clean steps - all inside the captured step.
@@ -263,6 +293,7 @@ class HipSegModel(object):
         if getattr(self, "_eval", None) is None:
             ep = graph.Plan(self.batch, self.dtype, str(self.device), training=False, class_metrics=self.class_metrics)
             ep.masked_loss = self._masked_loss()
+            ep.lovasz_softmax = self.w_lovasz_softmax
             ep.define(self._net(False, with_loss=True), share=self.plan)
             self._eval = ep
         return self._eval
@@ -621,6 +652,8 @@ class HipSegModel(object):
                 out["lovasz_loss"] = float(s[12])
             for k in self.unevaluated_terms:
                 out.pop(k, None)
+            if self.w_lovasz_softmax:
+                out[LOVASZ_SOFTMAX] = float(s[14])
         if self.masked:
             out["counted_pixels"] = float(s[12])      # n of stp_softmax_loss_masked: the pixels of the batch that are not ignore_label
         if self.class_metrics:

@@ -158,6 +158,9 @@ class Plan(object):
         # the softmax head's ignore label / class weights: {"ignore_label": .., "class_weights": ..} read by softmax_loss (set before
         # define, as loss_scale is), and the device tensor of the weights that launch reads
         self.masked_loss = None
+        # the softmax head's lovasz_softmax weight, read by softmax_loss (set before ``define``, as masked_loss is): non-zero adds the
+        # stp_lovasz_softmax launch behind the extended loss launch
+        self.lovasz_softmax = 0.0
         self.class_weights = None
         self.class_counts = None
         self.inputs = {}
@@ -1302,10 +1305,12 @@ class Plan(object):
             self._tape.append(back)
         return out
 
-    def _emit_loss(self, name, logits, target, dims, weights, tail=()):
+    def _emit_loss(self, name, logits, target, dims, weights, tail=(), then=None):
         """The tail the loss launches on logits share: the gradient buffer (None outside training), the weights (two floats, or the
         registry's five as a host array), `... gradC, loss_scale, workspace` [, ``tail``: the arguments an entry takes behind its
-        workspace], then the dynamic loss-scale multiplier.  Returns the gradient buffer."""
+        workspace], then the dynamic loss-scale multiplier.  ``then(dl)``: emits the launches that ADD to the scalars and the gradient
+        of this one (stp_lovasz_softmax) - behind it and in front of stp_scale_by_device, so that the dynamic scale covers them too.
+        Returns the gradient buffer."""
         dl = self._gradbuf(logits) if self.training else None
         if len(weights) == 5:
             self._loss_weights = (C.c_float * 5)(*weights)     # host array read at launch
@@ -1315,6 +1320,8 @@ class Plan(object):
         self._emit(self.fwd, name, logits.buf.data_ptr(), target.buf.data_ptr(), *dims, self.cdt, *weights, self.loss_scalars.data_ptr(),
                    dl.data_ptr() if dl is not None else None, logits.gradC, float(self.loss_scale), self.ws_loss.data_ptr(),
                    self.ws_loss.numel() * 4, *tail)
+        if then is not None:
+            then(dl)
         if self.training and self.dls is not None:
             self._emit(self.fwd, "stp_scale_by_device", dl.data_ptr(), logits.rows * logits.gradC, self.cdt, self.dls.data_ptr(), self.dls.data_ptr() + 16)
         return dl
@@ -1391,7 +1398,8 @@ class Plan(object):
         one-hot target: stp_softmax_loss_ex] (target = class index per pixel).  ``Plan.masked_loss`` = {"ignore_label": 0..255 or None,
         "class_weights": one positive float per class or None} (set before define, as loss_scale is; the parameter list above is
         pinned by tests/test_softmax_losses_host.py): stp_softmax_loss_masked (include/stp_hip.h has the arithmetic); None: the plan
-        of before."""
+        of before.  ``Plan.lovasz_softmax`` (a weight, set the same way; 0: the plan of before): the extended full-resolution branch with
+        one stp_lovasz_softmax launch directly behind the loss launch."""
         if logits.C < 2:
             raise StpShapeError("categorical loss expects at least two classes")
         if self.dry:
@@ -1399,7 +1407,8 @@ class Plan(object):
         opts = self.masked_loss or {}
         ignore_label, class_weights = opts.get("ignore_label"), opts.get("class_weights")
         masked = ignore_label is not None or class_weights is not None
-        if masked or w_iou or w_jaccard or w_focal:
+        w_lovasz = float(self.lovasz_softmax or 0.0)
+        if masked or w_iou or w_jaccard or w_focal or w_lovasz:
             # one launch on the full-resolution logits: the extended loss, masked or not, has no low-resolution (_up) form, so FPN /
             # PSPNet keep their stp_resize_bilinear and its gradient launch
             name, tail, ign = "stp_softmax_loss_ex", (), None
@@ -1418,7 +1427,23 @@ class Plan(object):
                 name, tail = "stp_softmax_loss_masked", (ign, cw.data_ptr() if cw is not None else None)
             self.loss_scalars = self._alloc((16,), torch.float32)
             self.loss_scalars.zero_()
-            self._emit_loss(name, logits, target, (logits.rows, logits.C, logits.C), (w_cce, w_dice, w_iou, w_jaccard, w_focal), tail=tail)
+            then = None
+            if w_lovasz:
+                # Lovasz-Softmax: ADDS to scalars[0] and to the gradient the launch above wrote (include/stp_hip.h has the arithmetic); the
+                # static loss scale goes in as its grad_scale, class weights do not enter it
+                nbytes = int(self.lib.stp_lovasz_softmax_workspace_bytes(logits.rows, logits.C))
+                if nbytes <= 0:
+                    raise StpShapeError("lovasz_softmax: the sort workspace cannot be sized (2..32 classes, pixels * classes < 2^31, a device)")
+                self.ws_lovasz = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+                def then(dl):
+                    self._emit(self.fwd, "stp_lovasz_softmax", logits.buf.data_ptr(), target.buf.data_ptr(), logits.rows, logits.C, logits.C,
+                               self.cdt, w_lovasz, self.loss_scalars.data_ptr(), dl.data_ptr() if dl is not None else None, logits.gradC,
+                               float(self.loss_scale), -1 if ignore_label is None else int(ignore_label), self.ws_lovasz.data_ptr(), nbytes)
+            self._emit_loss(name, logits, target, (logits.rows, logits.C, logits.C), (w_cce, w_dice, w_iou, w_jaccard, w_focal), tail=tail,
+                            then=then)
+            if w_lovasz:
+                logits.meta["loss_bias_grad"] = False      # a later launch adds to the gradient: no bias gradient from the first one's workgroup sums
             self._emit_confusion(logits, target, ignore_label=ign)
             logits.grad_ready = self.training
             return
@@ -1507,6 +1532,10 @@ class Plan(object):
             elif name == "stp_lovasz_hinge" and done:
                 a = list(args)
                 a[2] = n_valid                            # images
+                _lib.check(fn(*a, st), name)
+            elif name == "stp_lovasz_softmax" and done:   # ADDS its term to the scalars the first launch wrote: re-run behind it
+                a = list(args)
+                a[2] = args[2] // self.N * n_valid        # pixels
                 _lib.check(fn(*a, st), name)
         if not done:
             raise _lib.StpError("the plan has no loss launch")

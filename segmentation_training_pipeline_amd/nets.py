@@ -127,7 +127,7 @@ def _loss(plan, logits, target, classes, loss, multilabel):
             raise ValueError("lovasz_loss is not available for a multi-label head")
         plan.sigmoid_multilabel_loss(logits, target, *loss[:5])
     else:
-        plan.softmax_loss(logits, target, *loss[:5])      # (ignore_label / class_weights: Plan.masked_loss)
+        plan.softmax_loss(logits, target, *loss[:5])      # (ignore_label / class_weights: Plan.masked_loss; lovasz_softmax: Plan.lovasz_softmax)
 
 
 def _head(plan, x, H, W, classes, loss, with_loss, multilabel=False):

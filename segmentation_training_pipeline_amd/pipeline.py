@@ -50,7 +50,7 @@ def aug_list(spec):
 def metric_mode(name, mode="auto"):
     if mode in ("min", "max"):
         return mode
-    return "min" if "loss" in name else "max"
+    return "min" if ("loss" in name or "lovasz" in name) else "max"      # (lovasz_softmax is a loss without the word)
 
 
 # Keras logs a metric under the NAME OF ITS FUNCTION: the registry of segmentation.py:15-22 maps `iou` -> iou_coef,
@@ -676,7 +676,7 @@ def _feed_block(self, plan, hb):
 DeviceFeeder._feed_block = _feed_block
 
 
-def derived_metrics(scal, classes=1, extended=False, activation=None, unlogged=()):
+def derived_metrics(scal, classes=1, extended=False, activation=None, unlogged=(), logged=()):
     """scal: the loss scalars of stp_sigmoid_bce_dice -> Keras-style log entries (metric names of
     schemas/segmentation.raml:98-105: binary_accuracy, dice, iou, iot).  ``extended``: the loss names one of the other registry
     entries (stp_sigmoid_loss_ex / stp_lovasz_hinge / stp_sigmoid_multilabel_loss / stp_softmax_loss_ex leave them in scalars 10..12): they are logged too, so that
@@ -684,7 +684,9 @@ def derived_metrics(scal, classes=1, extended=False, activation=None, unlogged=(
     activation: a multi-label sigmoid head (``activation="sigmoid"``, classes > 1) logs binary_crossentropy, a softmax head
     categorical_crossentropy; only the one-class head has lovasz_loss.  ``unlogged``: names left out because the loss kernel did not
     evaluate them (``HipSegModel.unevaluated_terms``: focal_loss of a softmax head whose spec gives it no weight - stp_softmax_loss_ex
-    skips the term, and a constant 0 must not be logged, monitored or selected on)."""
+    skips the term, and a constant 0 must not be logged, monitored or selected on).  ``logged``: the other half of that mechanism - names
+    added because a further launch evaluated them (``HipSegModel.evaluated_terms``: lovasz_softmax of a softmax head whose spec gives it a
+    weight, stp_lovasz_softmax leaves it in scalars[14]); a model that does not name the term logs what it always did."""
     loss, bce, dice_l, dice_m, acc, _sp, _sy, _spy, iou, iot = (float(v) for v in scal[:10])
     multilabel = is_multilabel(classes, activation)
     out = {"loss": loss, ("binary_crossentropy" if classes == 1 or multilabel else "categorical_crossentropy"): bce, "dice_loss": dice_l,
@@ -695,6 +697,8 @@ def derived_metrics(scal, classes=1, extended=False, activation=None, unlogged=(
             out["lovasz_loss"] = float(scal[12])
         for k in unlogged:
             out.pop(k, None)
+        if "lovasz_softmax" in logged and len(scal) >= 15:
+            out["lovasz_softmax"] = float(scal[14])
     return out
 
 
@@ -708,6 +712,10 @@ def _activation(model):
 
 def _unlogged(model):
     return tuple(getattr(model, "unevaluated_terms", ()))
+
+
+def _logged(model):
+    return tuple(getattr(model, "evaluated_terms", ()))
 
 
 def _class_metrics(model):
@@ -793,7 +801,7 @@ class Trainer(object):
         sums = {}
         if snaps:
             for scal, n in zip(torch.stack(snaps).cpu().numpy(), counts):
-                for k, v in derived_metrics(scal, getattr(m, "classes", 1), _extended(m), _activation(m), _unlogged(m)).items():
+                for k, v in derived_metrics(scal, getattr(m, "classes", 1), _extended(m), _activation(m), _unlogged(m), _logged(m)).items():
                     sums[k] = sums.get(k, 0.0) + v * n
         if conf is not None:
             sums[CONFUSION_KEY] = conf.cpu().numpy()
@@ -804,25 +812,25 @@ class Trainer(object):
         the same values bit for bit."""
         sums, n = self.run_epoch_sums(indexes, training)
         return reduce_epoch_sums(sums, n, getattr(self.model, "classes", 1), _extended(self.model), _activation(self.model), _unlogged(self.model),
-                                 _class_metrics(self.model))
+                                 _class_metrics(self.model), _logged(self.model))
 
 
 CONFUSION_KEY = "confusion"      # run_epoch_sums: the epoch's confusion matrix (int64 [classes * classes]) rides in the sums under this key
 
 
-def epoch_log_names(classes=1, extended=False, activation=None, unlogged=(), class_metrics=False):
+def epoch_log_names(classes=1, extended=False, activation=None, unlogged=(), class_metrics=False, logged=()):
     """``class_metrics``: the model counts the confusion matrix (HipSegModel.class_metrics): categorical_accuracy, mean_iou, iou_class_k."""
-    names = list(derived_metrics(np.zeros(16, np.float32), classes, extended, activation, unlogged))
+    names = list(derived_metrics(np.zeros(16, np.float32), classes, extended, activation, unlogged, logged))
     return sorted(names + (class_metric_names(classes) if class_metrics else []))
 
 
-def reduce_epoch_sums(sums, n, classes=1, extended=False, activation=None, unlogged=(), class_metrics=False):
+def reduce_epoch_sums(sums, n, classes=1, extended=False, activation=None, unlogged=(), class_metrics=False, logged=()):
     """{name: weighted sum}, samples -> {name: mean over the samples of ALL ranks}.  The vector layout is fixed by the
     metric names (not by what a rank happened to see), so a rank with an empty shard still takes part in the collective.
     ``class_metrics``: the classes^2 entries of the epoch's confusion matrix follow the sample count (zeros from a rank that saw
     nothing; integers below 2^53 are exact in the float64 vector); the class metrics are ratios of the SUMMED matrix, not means of
     per-batch ratios."""
-    names = epoch_log_names(classes, extended, activation, unlogged)
+    names = epoch_log_names(classes, extended, activation, unlogged, logged=logged)
     vec = [sums.get(k, 0.0) for k in names] + [float(n)]
     if class_metrics:
         conf = sums.get(CONFUSION_KEY)
@@ -1098,7 +1106,7 @@ class GenericTaskConfig(object):
         # primary_metric / callback monitors are checked against the names an epoch will log BEFORE the first epoch trains (a typo used
         # to surface only after a whole epoch: advisor finding, round 3)
         known = {}
-        for k in epoch_log_names(self.classes, _extended(impl), _activation(impl), _unlogged(impl), _class_metrics(impl)) + ["lr"]:
+        for k in epoch_log_names(self.classes, _extended(impl), _activation(impl), _unlogged(impl), _class_metrics(impl), _logged(impl)) + ["lr"]:
             known[k] = 0.0
             known["val_" + k] = 0.0
         for what, name in [("primary_metric", self.primary_metric)] + [("%s.monitor" % type(cb).__name__, cb.monitor) for cb in cbs if hasattr(cb, "monitor")]:
