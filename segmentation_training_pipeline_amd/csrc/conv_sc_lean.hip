@@ -1000,7 +1000,7 @@ int stem_lean_launch(const StemArgs& a, hipStream_t s) {
 // the 32 pixels of a tile row, fragments by transpose reads: A = dY^T (wave w owns output channels 16 w .. 16 w + 15: no cross-wave
 // reduction), B = 32 pixels x 16 columns, the 16 columns being FOUR taps kw x 4 channels = 32 contiguous bytes of the patch.  A B
 // fragment of patch row r serves every (tile row, kh) pair with 2 * row + kh = r: 52 + 8 transpose reads for 56 MFMAs per tile and wave.
-// One fp32 slab [64][224] per workgroup, summed by the generic fixed-order reduce kernel (the small-channel plan of conv_wgrad.hip).
+// One fp32 slab [64][224] per workgroup, summed by the generic fixed-order reduce kernel (the small-channel plan of conv_wgrad.hip: plan_wgrad).
 // =================================================================================================
 constexpr int SWG_TH = 4, SWG_PH = 2 * (SWG_TH - 1) + 7;                      // tile rows, patch rows (13)
 constexpr int SWG_NVX = SWG_PH * STL_VPR, SWG_NPX = (SWG_NVX + 255) / 256;    // patch vectors / passes

@@ -139,7 +139,7 @@ class Plan(object):
         # (stp_conv_params.src_bn_mean), the normalised tensor is never written
         self.fuse_bn_sc = os.environ.get("STP_FUSE_BN_SC", "1") != "0"
         # producer BatchNormalization applied in LDS by the halo kernel (needs its automatic selection: STP_HALO != 0) AND by the
-        # weight gradient of the same layer (row-of-taps kernel, single-layer or grouped: conv_wgrad.hip's PBN instances): the
+        # weight gradient of the same layer (row-of-taps kernel, single-layer or grouped: conv_wgrad_row.hip's PBN instances): the
         # normalised tensor is never written, the stp_bn_apply launch disappears.  OPT-IN (STP_FUSE_BN_HALO=1): measured slower in
         # round 1 (the weight gradient still read the normalised tensor) and again in round 4 with the grouped weight gradient
         # normalising its operand itself (profiles/r04b_*): 6.99 vs 6.79 ms per step on one box.  The launches it removes cost
@@ -378,7 +378,7 @@ class Plan(object):
         * every consumer is a small-channel convolution (conv_sc.hip / conv_sc_wgrad.hip: forward AND weight gradient normalise the pre-BN tensor
           while staging it): the stp_bn_apply launch is dropped; ``tensor(name)`` still materialises the tensor on demand;
         * some consumers are halo-kernel convolutions (conv_halo.hip: the forward normalises the slab in LDS): when every one of
-          their weight gradients runs on the row-of-taps kernel (conv_wgrad.hip normalises its halo tile the same way) the launch
+          their weight gradients runs on the row-of-taps kernel (conv_wgrad_row.hip normalises its halo tile the same way) the launch
           is dropped as well; otherwise a weight gradient still reads the normalised tensor and the stp_bn_apply launch stays, a
           launch of its own (returned: the ids of these records, which _fuse_bn_finalize leaves alone).
 

@@ -1,4 +1,4 @@
-"""Float64 numpy restatement of the convolution weight gradient (csrc/conv_wgrad.hip, the small-channel and stem kernels of
+"""Float64 numpy restatement of the convolution weight gradient (csrc/conv_wgrad*.hip, the small-channel and stem kernels of
 conv_sc_wgrad.hip / conv_sc_lean.hip), shared by tests/test_wgrad_reference_host.py and tests/test_wgrad_ops_gpu.py.  Not collected, calls no
 kernel, no torch, no autograd: it is written from the index formula of include/stp_hip.h,
 
@@ -202,7 +202,7 @@ def fill_params(P, case, dtype, src0, dy, dw, src1=None, bn=None, accumulate=0):
 
 
 def row_eligible(case, dtype):
-    """wgrad_row_eligible of conv_wgrad.hip restated (variant 4 runs exactly on these)."""
+    """wgrad_row_eligible of conv_wgrad_row.hip restated (variant 4 runs exactly on these)."""
     g = geometry(case)
     return (dtype != "fp32" and case.kh == 3 and case.kw == 3 and case.s == 1 and case.p == 1 and case.c0 % 64 == 0 and case.c1 % 64 == 0 and
             case.co % 8 == 0 and (g["Wo"] % 64 == 0 or (g["Wo"] >= 16 and 64 % g["Wo"] == 0 and (g["Ho"] * g["Wo"]) % 64 == 0)))

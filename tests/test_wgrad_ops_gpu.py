@@ -1,4 +1,4 @@
-"""GPU op tests of the weight-gradient kernels (csrc/conv_wgrad.hip and the small-channel / stem kernels of conv_sc_wgrad.hip and
+"""GPU op tests of the weight-gradient kernels (csrc/conv_wgrad*.hip and the small-channel / stem kernels of conv_sc_wgrad.hip and
 conv_sc_lean.hip), in fp32 and in both 16-bit builds.  Every entry point is called directly and compared with the float64 numpy
 restatement of tests/_wgrad_reference.py - never with a second kernel, and with no tolerance scaled by a tensor's largest element or
 taken from a kernel's output:
