@@ -1162,6 +1162,49 @@ int stp_label_select(const int32_t* labels, int32_t h, int32_t w, int32_t label_
                      int64_t min_area, int32_t conf_num, int32_t conf_den, int32_t* out_labels, int32_t* count, int64_t* out_sums,
                      int32_t* out_boxes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * U-Net border weight maps on the device (csrc/border_weight.hip) and the one-class loss that takes them (csrc/loss_sigmoid.hip):
+ *   w(x) = w_c(x) + w0 * exp(-(d1(x) + d2(x))^2 / (2 sigma^2))      (Ronneberger et al. 2015, eq. 2)
+ * with d1, d2 the distances from a background pixel to the nearest and the second-nearest object, truncated to a window.  int32 and fp32
+ * only (both builds export the same code); the distances are exact integer work, equal to the host statement
+ * (tests/_border_weight_reference.py); no atomics, no workgroup waits for another, byte-identical from run to run.  STP_E_BADARG before any
+ * launch for a NULL pointer (d1sq, d2sq may be NULL), N, H or W < 1, N * H * W >= 2^31, radius outside 1..32, w0 < 0, sigma <= 0, b0 or
+ * b1 <= 0 or any of them not finite; never a synchronisation or an allocation; workspace 8-byte aligned and >=
+ * stp_border_weight_workspace_bytes(N, H, W) (0 for sizes it refuses), else STP_E_WORKSPACE.
+ *
+ *   labels  : int32 [N][H][W], 0 on the background, > 0 on objects; ANY image with values >= 0, not only stp_mask_label's.  Two pixels
+ *             with different non-zero values belong to different objects (neighbours too); equal values are one object.
+ *   window  : for a pixel p of sample n, the pixels q of the SAME sample with |qy - py| <= R and |qx - px| <= R (R = radius), clipped to
+ *             the image.  It never reaches into the neighbouring sample of the batch.
+ *   D1^2(p) : the smallest |p - q|^2 over the labelled pixels of the window (int32); L1 = the label of one such nearest pixel (a tie
+ *             between labels may be broken either way: nothing below depends on it).  A foreground pixel is its own nearest: D1^2 = 0.
+ *   D2^2(p) : the smallest |p - q|^2 over the labelled pixels of the window whose label differs from L1.
+ *             Either is -1 when no such pixel exists.
+ *   term(p) = w0 * exp(-(sqrt(D1^2) + sqrt(D2^2))^2 / (2 sigma^2)) on the background where D2^2 >= 0, else 0.
+ *   weights[p] = (labels[p] ? b1 : b0) + term(p), evaluated in fp32 (class_balance = (b0, b1)).
+ *   The window truncates the usual statement (per label distance_transform_edt, the two smallest): a pixel the window drops has
+ *   d2 >= R + 1, so the two differ by less than w0 * exp(-(R + 1)^2 / (2 sigma^2)).
+ *   Separable and still exact, 2 launches over the whole batch: rows (per pixel the nearest labelled pixel of its row within +-R as
+ *   (dxA, labelA) and the nearest one whose label != labelA as dxB, 8 bytes per pixel in the workspace), columns (dy in -R..R twice:
+ *   (D1^2, L1) from the A candidates, then per row dxA if labelA != L1, else dxB).
+ *   d1sq, d2sq : int32 [N][H][W] or NULL: D1^2 and D2^2, all written.
+ *
+ *   stp_sigmoid_bce_dice_weighted : stp_sigmoid_bce_dice with a pixel-weight operand, pixel_weights fp32 [count], every one > 0 (the map
+ *             above).  weighted_binary_crossentropy = sum_i w_i * bce_i / count (the Keras sample-weight rule; no zero weights, so its
+ *             non-zero-weight normaliser is 1), bce_i the sibling's expression, clip included;
+ *             loss = w_bce * weighted_binary_crossentropy + w_dice * dice_loss.  The weights enter neither dice_loss nor any logged
+ *             overlap or accuracy.  scalars (fp32[16]): [0..9] as the sibling with [0] the loss above and [1] the UNWEIGHTED
+ *             binary_crossentropy, [13] weighted_binary_crossentropy, [15] the mean of the weights; [10..12], [14] are not written.
+ *             dlogits: the sibling's, the cross-entropy part multiplied by w_i, then by grad_scale; padding channels exactly 0.
+ *             Deterministic (fixed-order reduction, no atomics).  Workspace: stp_loss_workspace_bytes().  It leaves no bias-gradient sums
+ *             (stp_sigmoid_loss_bias_grad does not follow it).  BADARG as the sibling, and for NULL pixel_weights. */
+size_t stp_border_weight_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int stp_border_weight(const int32_t* labels, int32_t N, int32_t H, int32_t W, float w0, float sigma, int32_t radius, float b0, float b1,
+                      float* weights, int32_t* d1sq, int32_t* d2sq, void* workspace, size_t workspace_bytes, void* stream);
+int stp_sigmoid_bce_dice_weighted(const void* logits, const uint8_t* target, int64_t count, int32_t dtype, float w_bce, float w_dice,
+                                  float* scalars, void* dlogits, int32_t dl_channels, float grad_scale, void* workspace,
+                                  size_t workspace_bytes, const float* pixel_weights, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,10 @@ SIGNATURES = {
     "stp_label_measure": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "stp_label_select_workspace_bytes": (sz, [i32]),
     "stp_label_select": (i32, [vp, i32, i32, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "stp_border_weight_workspace_bytes": (sz, [i32, i32, i32]),
+    "stp_border_weight": (i32, [vp, i32, i32, i32, f32, f32, i32, f32, f32, vp, vp, vp, vp, sz, vp]),
+    # stp_sigmoid_bce_dice's list with the pixel weights in front of the stream
+    "stp_sigmoid_bce_dice_weighted": (i32, [vp, vp, i64, i32, f32, f32, vp, vp, i32, f32, vp, sz, vp, vp]),
 }
 
 _libs = {}          # storage format ("bf16" | "fp16") -> loaded library

@@ -145,12 +145,73 @@ def check_masked_loss(ignore_label, class_weights, classes, architecture, head_a
     return ignore_label, class_weights
 
 
+BORDER_WEIGHT_TERMS = ("weighted_binary_crossentropy", "border_weight_mean")      # stp_sigmoid_bce_dice_weighted: scalars[13], [15]
+BORDER_WEIGHT_MAX_RADIUS = 32
+BORDER_WEIGHT_DEFAULTS = {"w0": 10.0, "sigma": 5.0, "class_balance": (1.0, 1.0)}   # radius: ceil(4 sigma)
+
+
+def border_weight_params(w0=10.0, sigma=5.0, radius=None, class_balance=(1.0, 1.0)):
+    """The parameters of the U-Net border weight map (include/stp_hip.h) -> {"w0", "sigma", "radius", "class_balance": (b0, b1)}, checked:
+    w0 >= 0, sigma > 0, both balances > 0, all finite; radius an integer 1..32, by default ceil(4 sigma).  ValueError otherwise."""
+    def number(name, v, positive):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) \
+                or (v <= 0 if positive else v < 0):
+            raise ValueError("border_weights: %s must be a finite number %s 0, not %r" % (name, ">" if positive else ">=", v))
+        return float(v)
+    w0, sigma = number("w0", w0, False), number("sigma", sigma, True)
+    try:
+        b = tuple(class_balance)
+    except TypeError:
+        b = ()
+    if len(b) != 2:
+        raise ValueError("border_weights: class_balance is [weight of the background, weight of the objects], not %r" % (class_balance,))
+    b = (number("class_balance[0]", b[0], True), number("class_balance[1]", b[1], True))
+    if radius is None:
+        radius = int(np.ceil(4.0 * sigma))
+        if radius > BORDER_WEIGHT_MAX_RADIUS:
+            raise ValueError("border_weights: the default radius ceil(4 * sigma) = %d exceeds %d for sigma = %g: name a radius of 1..%d "
+                             "(the map is then truncated at it)" % (radius, BORDER_WEIGHT_MAX_RADIUS, sigma, BORDER_WEIGHT_MAX_RADIUS))
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= BORDER_WEIGHT_MAX_RADIUS:
+        raise ValueError("border_weights: radius must be an integer 1..%d, not %r" % (BORDER_WEIGHT_MAX_RADIUS, radius))
+    return {"w0": w0, "sigma": sigma, "radius": int(radius), "class_balance": b}
+
+
+def _loss_names(spec):
+    """The names a composite ``a+w*b`` loss spec mentions, whatever their weights."""
+    return [t.split("*", 1)[1].strip() if "*" in t else t.strip() for t in str(spec).split("+")]
+
+
+def check_border_weights(border_weights, classes=1, architecture=None, head_activation="sigmoid", multilabel=False, loss="binary_crossentropy"):
+    """The ``border_weights`` key -> None (absent, None or False) or the checked parameters of ``border_weight_params`` (``True``: the
+    defaults).  ValueError for what the backend cannot train that way: the map weights the binary_crossentropy of a one-class sigmoid
+    head on Unet, Linknet, FPN or PSPNet, next to an unweighted dice_loss."""
+    if border_weights is None or border_weights is False:
+        return None
+    if multilabel or head_activation != "sigmoid" or int(classes) != 1:
+        raise ValueError("border_weights need a one-class sigmoid head (classes: 1, activation: sigmoid); this is a %s head"
+                         % ("multi-label sigmoid" if multilabel else "softmax"))
+    if architecture == "DeepLabV3":
+        raise ValueError("border_weights are not available for DeepLabV3 (its loss runs on probabilities): use Unet, Linknet, FPN or PSPNet")
+    other = [n for n in _loss_names(loss) if n not in ("binary_crossentropy", "dice_loss")]
+    if other:
+        raise ValueError("border_weights weight binary_crossentropy only: the loss may name binary_crossentropy and dice_loss, not %s"
+                         % ", ".join(other))
+    if border_weights is True:
+        return border_weight_params()
+    if not isinstance(border_weights, dict):
+        raise ValueError("border_weights is `true` or a mapping {w0, sigma, radius, class_balance}, not %r" % (border_weights,))
+    unknown = sorted(set(border_weights) - {"w0", "sigma", "radius", "class_balance"})
+    if unknown:
+        raise ValueError("border_weights: unknown key(s) %s (have: w0, sigma, radius, class_balance)" % ", ".join(map(str, unknown)))
+    return border_weight_params(**border_weights)
+
+
 class HipSegModel(object):
     def __init__(self, architecture="Unet", backbone="resnet34", input_shape=(512, 512, 3), classes=1, activation="sigmoid",
                  batch=16, dtype="bf16", loss="binary_crossentropy", optimizer="Adam", lr=1e-3, freeze_encoder=False,
                  decoder_filters=(256, 128, 64, 32, 16), clipnorm=None, clipvalue=None, use_graph=True, device="cuda",
                  opt_kwargs=None, seed=42, decoder_block_type="upsampling", net_kwargs=None, loss_scale=None, class_metrics=False,
-                 ignore_label=None, class_weights=None):
+                 ignore_label=None, class_weights=None, border_weights=None):
         if architecture not in nets.NETWORKS:
             raise ValueError("Unknown architecture")
         if backbone not in nets.known_backbones() or (backbone in nets.VGG_BLOCKS and architecture not in ("Unet", "Linknet", "FPN", "PSPNet")) \
@@ -176,6 +237,9 @@ class HipSegModel(object):
         self.ignore_label, self.class_weights = check_masked_loss(ignore_label, class_weights, classes, architecture, self.head_activation,
                                                                   self.multilabel)
         self.masked = self.ignore_label is not None or self.class_weights is not None
+        # border_weights (one-class sigmoid heads of Unet / Linknet / FPN / PSPNet): the U-Net weight map on the cross-entropy
+        # (stp_border_weight + stp_sigmoid_bce_dice_weighted), checked before any device work
+        self.border_weights = check_border_weights(border_weights, classes, architecture, self.head_activation, self.multilabel, loss)
         self.architecture, self.backbone = architecture, backbone
         self.H, self.W, self.in_ch = int(input_shape[0]), int(input_shape[1]), int(input_shape[2])
         self.classes, self.batch, self.dtype = classes, int(batch), dtype
@@ -193,6 +257,8 @@ class HipSegModel(object):
         # and the terms a further launch evaluates because the spec gives them a weight, logged on top (pipeline.derived_metrics ``logged``)
         self.w_lovasz_softmax = lovasz_softmax_weight(self.loss_w)
         self.evaluated_terms = (LOVASZ_SOFTMAX,) if self.w_lovasz_softmax else ()
+        if self.border_weights:
+            self.evaluated_terms += BORDER_WEIGHT_TERMS
         self.optimizer = optimizer.lower()
         if self.optimizer not in ("adam", "sgd", "rmsprop", "nadam"):
             raise ValueError("optimizer %r is not available in the HIP backend (have: SGD, Adam, RMSprop, Nadam)" % optimizer)
@@ -226,6 +292,7 @@ class HipSegModel(object):
         self.plan.loss_scale = self.loss_scale
         self.plan.masked_loss = self._masked_loss()
         self.plan.lovasz_softmax = self.w_lovasz_softmax
+        self.plan.border_weights = self.border_weights
         # DYNAMIC re-scaling on top of the static scale (fp16 only; STP_DYNAMIC_LOSS_SCALE=0 keeps the static scale + skip-on-overflow of
         # round 3): a device multiplier m (float[8] record, include/stp_hip.h) applied to the loss gradient right after the loss kernel,
         # halved when a step is skipped, doubled after `interval` clean steps - all inside the captured step.
@@ -294,6 +361,7 @@ class HipSegModel(object):
             ep = graph.Plan(self.batch, self.dtype, str(self.device), training=False, class_metrics=self.class_metrics)
             ep.masked_loss = self._masked_loss()
             ep.lovasz_softmax = self.w_lovasz_softmax
+            ep.border_weights = self.border_weights
             ep.define(self._net(False, with_loss=True), share=self.plan)
             self._eval = ep
         return self._eval
@@ -654,6 +722,8 @@ class HipSegModel(object):
                 out.pop(k, None)
             if self.w_lovasz_softmax:
                 out[LOVASZ_SOFTMAX] = float(s[14])
+        if self.border_weights:
+            out["weighted_binary_crossentropy"], out["border_weight_mean"] = float(s[13]), float(s[15])
         if self.masked:
             out["counted_pixels"] = float(s[12])      # n of stp_softmax_loss_masked: the pixels of the batch that are not ignore_label
         if self.class_metrics:

@@ -317,6 +317,111 @@ extern "C" int stp_sigmoid_loss_ex(const void* logits, const uint8_t* target, in
   return STP_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// stp_sigmoid_bce_dice with a pixel-weight operand (the border weight map of border_weight.hip; include/stp_hip.h has the arithmetic):
+// the cross-entropy term is sum w_i bce_i / count, everything else - dice_loss, the logged overlaps, the accuracy and scalars[1], the
+// UNWEIGHTED cross-entropy - is the sibling's.  16-wide partial rows with two more sums:
+//   7 w_i * bce_i   8 w_i
+// The gradient pass leaves no bias-gradient sums: stp_sigmoid_loss_bias_grad does not follow this entry.
+template <typename T>
+__global__ __launch_bounds__(256) void loss_weighted_partial_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ target,
+                                                                    const float* __restrict__ pw, int64_t count, float* partial) {
+  float a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  auto one = [&a](float z, bool tgt, float wt) __attribute__((always_inline)) {
+    const float y = tgt ? 1.f : 0.f;
+    const float p = 1.f / (1.f + __expf(-z));
+    const float bce = keras_bce_fast(p, y);
+    a[0] += bce;
+    a[1] += p;
+    a[2] += y;
+    a[3] += p * y;
+    const float t = p > 0.5f ? 1.f : 0.f;
+    a[4] += t;
+    a[5] += t * y;
+    a[6] += (t == y) ? 1.f : 0.f;
+    a[7] += wt * bce;
+    a[8] += wt;
+  };
+  // four pixels per thread and iteration (8 or 16 bytes of logits, 4 of target, 16 of weights) where the operands allow it
+  if ((count & 3) == 0 && ((uintptr_t)logits & (4 * sizeof(T) - 1)) == 0 && ((uintptr_t)target & 3) == 0 && ((uintptr_t)pw & 15) == 0) {
+    const int64_t groups = count >> 2, per = (groups + gridDim.x - 1) / gridDim.x;
+    const int64_t g0 = (int64_t)blockIdx.x * per, g1 = g0 + per < groups ? g0 + per : groups;
+    for (int64_t g = g0 + threadIdx.x; g < g1; g += 256) {
+      const f32x4 z = load4(logits + g * 4), wt = load4(pw + g * 4);
+      const uint32_t tt = *reinterpret_cast<const uint32_t*>(target + g * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) one(z[e], ((tt >> (8 * e)) & 0xffu) != 0, wt[e]);
+    }
+  } else {
+    const int64_t per = (count + gridDim.x - 1) / gridDim.x;
+    const int64_t i0 = (int64_t)blockIdx.x * per, i1 = i0 + per < count ? i0 + per : count;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) one(Elem<T>::load(logits + i), target[i] != 0, pw[i]);
+  }
+  loss_block_sums<LOSS_NSUM_EX>(a, partial);
+}
+
+// scalars 0..9 as loss_finalize_kernel with [0] on the weighted cross-entropy, 13 weighted_binary_crossentropy, 15 the mean weight
+__global__ __launch_bounds__(256) void loss_weighted_finalize_kernel(const float* partial, int blocks, double inv_count, float w_bce,
+                                                                     float w_dice, float* scalars) {
+  const double* s = loss_finalize_sums<LOSS_NSUM_EX>(partial, blocks);
+  if (threadIdx.x != 0) return;
+  const LossTerms t = loss_common_scalars(s, inv_count, inv_count, scalars);
+  const double wbce = s[7] * inv_count;
+  scalars[0] = (float)(w_bce * wbce + w_dice * t.dice_l);
+  scalars[13] = (float)wbce;
+  scalars[15] = (float)(s[8] * inv_count);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void loss_weighted_grad_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ target,
+                                                                 const float* __restrict__ pw, int64_t count, const float* scalars,
+                                                                 float w_bce, float w_dice, float inv_count, float grad_scale,
+                                                                 T* __restrict__ dl, int dlc) {
+  const DiceIouGrad k(scalars);
+  const float den = k.den, inv_den2 = k.inv_den2, num = k.num;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) {
+    const float z = Elem<T>::load(logits + i);
+    const float y = target[i] ? 1.f : 0.f;
+    const float p = 1.f / (1.f + expf(-z));
+    const bool inr = (p >= 1e-7f) && (p <= 1.f - 1e-7f);
+    // d (w bce) / d z = w (p - y) where the probability clip is inactive
+    float g = inr ? w_bce * pw[i] * (p - y) * inv_count : 0.f;
+    g += w_dice * (-(2.f * y * den - num) * inv_den2) * (p * (1.f - p));
+    g *= grad_scale;
+    store_grad_row(dl + i * dlc, g, dlc);
+  }
+}
+
+extern "C" int stp_sigmoid_bce_dice_weighted(const void* logits, const uint8_t* target, int64_t count, int32_t dtype, float w_bce,
+                                             float w_dice, float* scalars, void* dlogits, int32_t dl_channels, float grad_scale,
+                                             void* workspace, size_t workspace_bytes, const float* pixel_weights, void* stream) {
+  const int rc = loss_check(dtype, logits && target && scalars && workspace && pixel_weights && count > 0, workspace_bytes,
+                            stp_loss_workspace_bytes());
+  if (rc != STP_OK) return rc;
+  if (dlogits && dl_channels < 1) return STP_E_BADARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int blocks = loss_value_blocks(count);
+  float* partial = (float*)workspace;
+  loss_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(loss_weighted_partial_kernel<T>, dim3(blocks), dim3(256), 0, s, (const T*)logits, target, pixel_weights, count, partial);
+  });
+  STP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss_weighted_finalize_kernel, dim3(1), dim3(256), 0, s, partial, blocks, 1.0 / (double)count, w_bce, w_dice, scalars);
+  STP_LAUNCH_CHECK();
+  if (dlogits) {
+    const int g = loss_grad_blocks(count, LOSS_GRAD_MAX_BLOCKS);
+    const float inv_count = (float)(1.0 / (double)count);
+    loss_by_dtype(dtype, [&](auto tag) {
+      using T = decltype(tag);
+      hipLaunchKernelGGL(loss_weighted_grad_kernel<T>, dim3(g), dim3(256), 0, s, (const T*)logits, target, pixel_weights, count, scalars, w_bce,
+                         w_dice, inv_count, grad_scale, (T*)dlogits, dl_channels);
+    });
+    STP_LAUNCH_CHECK();
+  }
+  return STP_OK;
+}
+
 
 template <typename T>
 __global__ void sigmoid_kernel(const T* __restrict__ logits, float* __restrict__ probs, int64_t count) {

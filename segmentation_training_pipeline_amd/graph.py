@@ -161,6 +161,10 @@ class Plan(object):
         # the softmax head's lovasz_softmax weight, read by softmax_loss (set before ``define``, as masked_loss is): non-zero adds the
         # stp_lovasz_softmax launch behind the extended loss launch
         self.lovasz_softmax = 0.0
+        # the one-class head's U-Net border weight map, read by sigmoid_loss (set before ``define``, as masked_loss is):
+        # {"w0", "sigma", "radius", "class_balance"} puts the label launches, stp_border_weight and the weighted loss launch in the place
+        # of stp_sigmoid_bce_dice; None: the plan of before
+        self.border_weights = None
         self.class_weights = None
         self.class_counts = None
         self.inputs = {}
@@ -1350,7 +1354,9 @@ class Plan(object):
 
     def sigmoid_loss(self, logits, target, w_bce, w_dice, w_iou=0.0, w_jaccard=0.0, w_focal=0.0, w_lovasz=0.0):
         """sigmoid + w_bce*binary_crossentropy + w_dice*dice_loss [+ w*iou_loss + w*jaccard_loss + w*focal_loss + w*lovasz_loss,
-        the rest of the registry at reference segmentation.py:15-22]; seeds the backward pass."""
+        the rest of the registry at reference segmentation.py:15-22]; seeds the backward pass.  ``Plan.border_weights`` (set before
+        define, as loss_scale is; the parameter list above stays): the cross-entropy weighted by the U-Net border weight map of the
+        target (_border_weighted_loss); None: the plan of before."""
         if logits.C != 1:
             raise StpShapeError("binary loss expects one class")
         if self.dry:
@@ -1358,6 +1364,9 @@ class Plan(object):
         self.loss_scalars = self._alloc((16,), torch.float32)
         self.loss_scalars.zero_()
         count = logits.rows
+        if self.border_weights:
+            self._border_weighted_loss(logits, target, w_bce, w_dice, w_iou or w_jaccard or w_focal or w_lovasz)
+            return
         if w_iou or w_jaccard or w_focal:
             dl = self._emit_loss("stp_sigmoid_loss_ex", logits, target, (count,), (w_bce, w_dice, w_iou, w_jaccard, w_focal))
         else:
@@ -1375,6 +1384,37 @@ class Plan(object):
             self._emit(self.fwd, "stp_lovasz_hinge", logits.buf.data_ptr(), target.buf.data_ptr(), self.N, count // self.N, self.cdt,
                        float(w_lovasz), self.loss_scalars.data_ptr(), dl.data_ptr() if dl is not None else None, logits.gradC,
                        self.ws_lovasz.data_ptr(), nbytes)
+        logits.grad_ready = self.training
+
+    def _border_weighted_loss(self, logits, target, w_bce, w_dice, other_terms):
+        """``Plan.border_weights`` = {"w0", "sigma", "radius", "class_balance": (b0, b1)}: the one-class loss with the cross-entropy
+        weighted by the U-Net border weight map of the step's own (augmented) target, computed on the device (include/stp_hip.h has the
+        arithmetic).  In this order: N x stp_mask_label (connectivity 2, one per sample, one shared workspace and count word) into one
+        [N][H][W] label buffer, one stp_border_weight, then stp_sigmoid_bce_dice_weighted through _emit_loss.  The weighted gradient pass
+        leaves no per-workgroup sums, so the class convolution takes its bias gradient the general way."""
+        if other_terms:
+            raise StpShapeError("border_weights weight binary_crossentropy only: the loss may name binary_crossentropy and dice_loss")
+        bw = self.border_weights
+        H, W = target.H, target.W
+        if target.C != 1 or self.N * H * W != logits.rows:
+            raise StpShapeError("border_weights need a one-channel mask at the logits' resolution")
+        n_label = int(self.lib.stp_mask_label_workspace_bytes(H, W))
+        n_weight = int(self.lib.stp_border_weight_workspace_bytes(self.N, H, W))
+        if n_label <= 0 or n_weight <= 0:
+            raise StpShapeError("border_weights: the label / weight workspace cannot be sized for %d x %d x %d" % (self.N, H, W))
+        self.border_labels = self._alloc((self.N, H, W), torch.int32)
+        self.border_map = self._alloc((self.N, H, W), torch.float32)
+        self.border_count = self._alloc((4,), torch.int32)
+        ws_label = self._alloc(((n_label + 7) // 8,), torch.int64)
+        ws_weight = self._alloc(((n_weight + 7) // 8,), torch.int64)
+        for n in range(self.N):
+            self._emit(self.fwd, "stp_mask_label", target.buf.data_ptr() + n * H * W, H, W, 2, 0, self.border_labels.data_ptr() + 4 * n * H * W,
+                       self.border_count.data_ptr(), ws_label.data_ptr(), ws_label.numel() * 8)
+        b0, b1 = bw["class_balance"]
+        self._emit(self.fwd, "stp_border_weight", self.border_labels.data_ptr(), self.N, H, W, float(bw["w0"]), float(bw["sigma"]),
+                   int(bw["radius"]), float(b0), float(b1), self.border_map.data_ptr(), None, None, ws_weight.data_ptr(), ws_weight.numel() * 8)
+        self._emit_loss("stp_sigmoid_bce_dice_weighted", logits, target, (logits.rows,), (w_bce, w_dice), tail=(self.border_map.data_ptr(),))
+        logits.meta["loss_bias_grad"] = False
         logits.grad_ready = self.training
 
     def sigmoid_multilabel_loss(self, logits, target, w_bce, w_dice, w_iou=0.0, w_jaccard=0.0, w_focal=0.0):
@@ -1508,7 +1548,7 @@ class Plan(object):
 
     # loss launches whose third argument is the element / pixel count of the batch ([N, ...] -> the first n_valid samples)
     LOSS_LAUNCHES = ("stp_sigmoid_bce_dice", "stp_softmax_cce_dice", "stp_prob_bce_dice", "stp_sigmoid_loss_ex", "stp_prob_cce_dice",
-                     "stp_sigmoid_multilabel_loss", "stp_softmax_loss_ex", "stp_softmax_loss_masked")
+                     "stp_sigmoid_multilabel_loss", "stp_softmax_loss_ex", "stp_softmax_loss_masked", "stp_sigmoid_bce_dice_weighted")
 
     def rerun_loss(self, n_valid):
         """Re-evaluates the loss / metric reduction over the first ``n_valid`` samples only (an evaluation batch whose tail

@@ -671,3 +671,33 @@ def label_select(labels, h, w, label_cap, sums, boxes, min_area, conf_num, conf_
     _lib.call("stp_label_select", ptr(_dev(labels)), h, w, int(label_cap), ptr(_dev(sums)), ptr(_dev(boxes)), int(min_area), int(conf_num),
               int(conf_den), ptr(_dev(out_labels)), ptr(_dev(count)), ptr(_dev(out_sums)), ptr(_dev(out_boxes)), ptr(_dev(workspace)),
               _nbytes(workspace), stream())
+
+
+# U-Net border weight maps on the device (csrc/border_weight.hip): int32 label images [N, H, W] -> the fp32 weight map, and the one-class
+# loss that takes it (csrc/loss_sigmoid.hip)
+def border_weight_workspace_bytes(N, H, W):
+    return int(_lib.load().stp_border_weight_workspace_bytes(int(N), int(H), int(W)))
+
+
+def border_weight(labels, N, H, W, w0, sigma, radius, b0, b1, weights, workspace, d1sq=None, d2sq=None):
+    """``weights`` float32 [N, H, W] = (b1 on the labelled pixels, b0 elsewhere) + w0 * exp(-(d1 + d2)^2 / (2 sigma^2)) on the background,
+    d1 / d2 the distances to the nearest / second-nearest object of the int32 label images ``labels`` inside the (2 radius + 1)^2 window of
+    the pixel's own sample (include/stp_hip.h).  ``d1sq`` / ``d2sq``: int32 [N, H, W] or None, the squared distances (-1: none)."""
+    n = int(N) * int(H) * int(W)
+    if labels.numel() < n or weights.numel() < n or labels.dtype != torch.int32 or weights.dtype != torch.float32:
+        raise ValueError("border_weight: int32 labels and float32 weights of N x H x W")
+    for d in (d1sq, d2sq):
+        if d is not None and (d.dtype != torch.int32 or d.numel() < n):
+            raise ValueError("border_weight: d1sq / d2sq are int32 of N x H x W, or None")
+    _lib.call("stp_border_weight", ptr(_dev(labels)), int(N), int(H), int(W), float(w0), float(sigma), int(radius), float(b0), float(b1),
+              ptr(_dev(weights)), ptr(_dev(d1sq)), ptr(_dev(d2sq)), ptr(_dev(workspace)), _nbytes(workspace), stream())
+
+
+def sigmoid_bce_dice_weighted(logits, target, count, w_bce, w_dice, scalars, dlogits, dl_channels, grad_scale, workspace, pixel_weights):
+    """``sigmoid_bce_dice`` with the cross-entropy weighted per pixel by ``pixel_weights`` (float32 [count], > 0); ``scalars`` float32 [16]:
+    [13] weighted_binary_crossentropy, [15] the mean weight, [1] stays the unweighted binary_crossentropy."""
+    if pixel_weights is not None and (pixel_weights.dtype != torch.float32 or pixel_weights.numel() < count):
+        raise ValueError("sigmoid_bce_dice_weighted: float32 pixel weights, one per element")
+    _lib.call("stp_sigmoid_bce_dice_weighted", ptr(logits), ptr(target), count, dt(logits), float(w_bce), float(w_dice), ptr(scalars),
+              ptr(dlogits), dl_channels, float(grad_scale), ptr(workspace), workspace.numel() * workspace.element_size(),
+              ptr(pixel_weights), stream())

@@ -50,7 +50,8 @@ def aug_list(spec):
 def metric_mode(name, mode="auto"):
     if mode in ("min", "max"):
         return mode
-    return "min" if ("loss" in name or "lovasz" in name) else "max"      # (lovasz_softmax is a loss without the word)
+    # (lovasz_softmax and weighted_binary_crossentropy are losses without the word)
+    return "min" if ("loss" in name or "lovasz" in name or "weighted_binary_crossentropy" in name) else "max"
 
 
 # Keras logs a metric under the NAME OF ITS FUNCTION: the registry of segmentation.py:15-22 maps `iou` -> iou_coef,
@@ -699,6 +700,12 @@ def derived_metrics(scal, classes=1, extended=False, activation=None, unlogged=(
             out.pop(k, None)
         if "lovasz_softmax" in logged and len(scal) >= 15:
             out["lovasz_softmax"] = float(scal[14])
+    # border_weights (a one-class head, stp_sigmoid_bce_dice_weighted: scalars[13], [15]); binary_crossentropy stays the unweighted term
+    if len(scal) >= 16:
+        if "weighted_binary_crossentropy" in logged:
+            out["weighted_binary_crossentropy"] = float(scal[13])
+        if "border_weight_mean" in logged:
+            out["border_weight_mean"] = float(scal[15])
     return out
 
 
@@ -900,6 +907,9 @@ class GenericTaskConfig(object):
         # softmax heads (keys of this backend): the label-image value left out of loss, gradient and metrics; one weight per class
         self.ignore_label = a.get("ignore_label")
         self.class_weights = a.get("class_weights")
+        # one-class sigmoid heads (a key of this backend): the U-Net border weight map on the cross-entropy, `true` or
+        # {w0, sigma, radius, class_balance}
+        self.border_weights = a.get("border_weights")
         self.gpus = int(a.get("gpus", 1))
         self.inference_batch = int(a.get("inference_batch", self.batch))
         self.showDataExamples = False
@@ -972,6 +982,8 @@ class GenericTaskConfig(object):
             extra["ignore_label"] = self.ignore_label
         if self.class_weights is not None:
             extra["class_weights"] = list(self.class_weights) if isinstance(self.class_weights, (list, tuple)) else self.class_weights
+        if self.border_weights is not None and self.border_weights is not False:
+            extra["border_weights"] = dict(self.border_weights) if isinstance(self.border_weights, dict) else self.border_weights
         model.compile(optimizer=self.optimizer, loss=loss, lr=lr, batch=self.batch, dtype=self.dtype, clipnorm=self.clipnorm,
                       clipvalue=self.clipvalue, metrics=self.metrics, device=device, use_graph=use_graph,
                       loss_scale=float(self.loss_scale) if self.loss_scale else None, **extra)
