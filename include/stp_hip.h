@@ -471,6 +471,22 @@ int stp_resize_bilinear(const void* x, void* y, int32_t N, int32_t H, int32_t W,
 size_t stp_resize_bilinear_bwd_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t factor);
 int stp_resize_bilinear_bwd(const void* dy, void* dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t factor, int32_t ldo,
                             int32_t coff, int32_t dtype, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* Which form of the gradient stp_resize_bilinear_bwd runs for these arguments (csrc/resize_bwd.hip; a plan-time query for callers and
+ * tests: launches nothing, needs no device).  The forms are tried in this order: SLICE_COPY (factor 1: the channel slice copied or
+ * added back), TINY (maps of <= 16 x 8 pixels, factor >= 8: a separable two-pass reduction; only with a workspace of the queried size
+ * and a 16-byte aligned dy), ROWS (output rows of <= 40 KB streamed through LDS: class logits), TILE (16-bit slices of >= 32
+ * channels: row pairs), then the workgroup-per-pixel kernel in one pass (BLOCK) or with its tap rows split over the workspace and summed
+ * by a second launch (BLOCK_SPLIT; without a large-enough workspace: BLOCK), and GATHER (channel counts or slices that no vector
+ * width divides).  STP_E_BADARG under the same checks as the launch; the pointers are only tested for null and alignment. */
+#define STP_RESIZE_BWD_GATHER 0
+#define STP_RESIZE_BWD_SLICE_COPY 1
+#define STP_RESIZE_BWD_TINY 2
+#define STP_RESIZE_BWD_ROWS 3
+#define STP_RESIZE_BWD_TILE 4
+#define STP_RESIZE_BWD_BLOCK 5
+#define STP_RESIZE_BWD_BLOCK_SPLIT 6
+int stp_resize_bilinear_bwd_form(const void* dy, const void* dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t factor, int32_t ldo,
+                                 int32_t coff, int32_t dtype, const void* workspace, size_t workspace_bytes);
 /* ResizeImage(factor, interpolation='nearest') (= UpSampling2D(factor)) with the same slice addressing, and its gradient (the sum of
  * the factor x factor outputs of every input pixel). */
 int stp_resize_nearest(const void* x, void* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t factor, int32_t ldo, int32_t coff,

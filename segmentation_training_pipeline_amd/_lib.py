@@ -146,6 +146,7 @@ SIGNATURES = {
     "stp_copy_cols_f32": (i32, [vp, i32, vp, i32, i32, i32, i32, vp]),
     "stp_resize_bilinear_bwd_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "stp_resize_bilinear_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "stp_resize_bilinear_bwd_form": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz]),
     "stp_resize_nearest": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "stp_resize_nearest_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "stp_channel_sum": (i32, [vp, i32, i64, i32, vp, i32, vp, sz, vp]),

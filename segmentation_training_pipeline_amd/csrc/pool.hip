@@ -443,30 +443,25 @@ __global__ __launch_bounds__(256) void avgpool_bwd_vec_kernel(const T* __restric
   stv<T, V>(d, o);
 }
 
+// the argument checks of stp_avgpool and stp_avgpool_bwd (a, b: the two tensors)
+static inline bool avgpool_args_ok(const void* a, const void* b, int N, int H, int W, int C, int k, int dtype) {
+  return stp_dtype_ok(dtype) && a && b && N > 0 && C > 0 && k >= 1 && !(H % k) && !(W % k);      // (the other build's 16-bit code, or garbage)
+}
+
 extern "C" size_t stp_avgpool_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t k) {
   if (N <= 0 || C <= 0 || k < 1 || H % k || W % k) return 0;
-  const int64_t nwin = (int64_t)N * (H / k) * (W / k);
-  size_t need = 0;
-  for (int V = 4; V <= 8; V += 4) {                      // either vector width the launch may pick
-    const int cg = ceil_div(C, V);
-    const int rps = split_rows(nwin * ceil_div(cg, pool_vl(cg)), k, k);
-    if (rps < k) need = std::max(need, (size_t)ceil_div(k, rps) * nwin * C * sizeof(float));
-  }
-  return need;
+  return split_bytes_either_width((int64_t)N * (H / k) * (W / k), C, k);
 }
 
 extern "C" int stp_avgpool(const void* x, void* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, int32_t dtype, void* workspace,
                            size_t workspace_bytes, void* stream) {
-  if (!stp_dtype_ok(dtype)) return STP_E_BADARG;      // (the other build's 16-bit code, or garbage)
-  if (!x || !y || N <= 0 || C <= 0 || k < 1 || H % k || W % k) return STP_E_BADARG;
-  if (dtype != STP_H16 && dtype != STP_F32) return STP_E_BADARG;
+  if (!avgpool_args_ok(x, y, N, H, W, C, k, dtype)) return STP_E_BADARG;
   const int V = vec_for(dtype, C, 0, 0);
   if (V > 1 && k * k >= 32) {
     const int cg = C / V, VL = pool_vl(cg);
     const int64_t nwin = (int64_t)N * (H / k) * (W / k);
-    int rps = split_rows(nwin * ceil_div(cg, VL), k, k);
-    int S = ceil_div(k, rps);
-    if (S > 1 && (!workspace || workspace_bytes < (size_t)S * nwin * C * sizeof(float))) { rps = k; S = 1; }   // no workspace: one pass
+    const SplitPlan sp = split_plan_fit(split_plan(nwin, C, cg, VL, k), k, workspace, workspace_bytes);
+    const int rps = sp.rps, S = sp.S;
     float* part = S > 1 ? (float*)workspace : nullptr;
     const dim3 grid((unsigned)nwin, ceil_div(cg, VL), S);
     const size_t lds = (size_t)(256 / VL) * VL * V * sizeof(float);
@@ -487,9 +482,7 @@ extern "C" int stp_avgpool(const void* x, void* y, int32_t N, int32_t H, int32_t
 
 extern "C" int stp_avgpool_bwd(const void* dy, void* dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, int32_t dtype,
                                int32_t accumulate, void* stream) {
-  if (!stp_dtype_ok(dtype)) return STP_E_BADARG;      // (the other build's 16-bit code, or garbage)
-  if (!dy || !dx || N <= 0 || C <= 0 || k < 1 || H % k || W % k) return STP_E_BADARG;
-  if (dtype != STP_H16 && dtype != STP_F32) return STP_E_BADARG;
+  if (!avgpool_args_ok(dy, dx, N, H, W, C, k, dtype)) return STP_E_BADARG;
   const int V = vec_for(dtype, C, 0, 0);
   if (V > 1 && (int64_t)N * H <= 65535) {
     const dim3 grid(ceil_div(W * (C / V), 256), N * H);
@@ -582,16 +575,14 @@ extern "C" int stp_avgpool_pyramid_ok(int32_t N, int32_t H, int32_t W, int32_t C
   const int k[4] = {k0, k1, k2, k3};
   return on && stp_dtype_ok(dtype) && pool_pyramid_ok(N, H, W, C, k, pool_pyramid_levels(k), dtype) ? 1 : 0;
 }
-// rows-per-split of the finest level's window launch (the table of fp32 sums is always written, also with one split)
-static int pool_pyramid_rps(int N, int H, int W, int C, int k0, int dtype) {
+// the split of the finest level's window launch (the table of fp32 sums is always written, also with one split)
+static SplitPlan pool_pyramid_split(int N, int H, int W, int C, int k0, int dtype) {
   const int V = vec_for(dtype, C, 0, 0), cg = C / V;
-  const int64_t nwin = (int64_t)N * (H / k0) * (W / k0);
-  return split_rows(nwin * ceil_div(cg, pool_vl(cg)), k0, k0);
+  return split_plan((int64_t)N * (H / k0) * (W / k0), C, cg, pool_vl(cg), k0);
 }
 extern "C" size_t stp_avgpool_pyramid_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t k0, int32_t dtype) {
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || k0 < 1 || H % k0 || W % k0 || (dtype != STP_H16 && dtype != STP_F32) || vec_for(dtype, C, 0, 0) <= 1) return 0;
-  const int S = ceil_div(k0, pool_pyramid_rps(N, H, W, C, k0, dtype));
-  return (size_t)S * N * (H / k0) * (W / k0) * C * sizeof(float);
+  return pool_pyramid_split(N, H, W, C, k0, dtype).bytes;
 }
 extern "C" int stp_avgpool_pyramid(const void* x, void* y0, void* y1, void* y2, void* y3, int32_t k0, int32_t k1, int32_t k2, int32_t k3, int32_t N,
                                    int32_t H, int32_t W, int32_t C, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
@@ -612,7 +603,8 @@ extern "C" int stp_avgpool_pyramid(const void* x, void* y0, void* y1, void* y2, 
   }
   const int V = vec_for(dtype, C, 0, 0), cg = C / V, VL = pool_vl(cg);
   p.nwin = (int64_t)N * (H / k0) * (W / k0);
-  const int rps = pool_pyramid_rps(N, H, W, C, k0, dtype), S = ceil_div(k0, rps);
+  const SplitPlan sp = pool_pyramid_split(N, H, W, C, k0, dtype);
+  const int rps = sp.rps, S = sp.S;
   float* part = (float*)workspace;
   const dim3 grid((unsigned)p.nwin, ceil_div(cg, VL), S);
   const size_t lds = (size_t)(256 / VL) * VL * V * sizeof(float);

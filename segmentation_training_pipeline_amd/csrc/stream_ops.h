@@ -1,6 +1,6 @@
-// Shared pieces of the HBM-bound streaming units bn.hip, pool.hip, resize.hip and elementwise.hip: the vector load / store
-// helpers, the per-channel partial-sum kernel and its fixed-order reduction, the grid rules, the one statement of the storage-type /
-// vector-width dispatch, and both sides (device tail, host launch pieces) of the gradient passes that complete a BatchNormalization
+// Shared pieces of the HBM-bound streaming units bn.hip, pool.hip, upsample2x.hip, resize.hip, resize_bwd.hip and elementwise.hip: the
+// vector load / store helpers, the per-channel partial-sum kernel and its fixed-order reduction, the grid rules, the one statement of the
+// storage-type / vector-width dispatch, the one statement of a tap reduction split over a workspace (SplitPlan), and both sides (device tail, host launch pieces) of the gradient passes that complete a BatchNormalization
 // backward.  Everything here is a template, __forceinline__ or static inline: a unit that includes it gets only what it uses.
 #pragma once
 #include "common.h"
@@ -205,6 +205,12 @@ static inline int vec_for(int dtype, int a, int b, int c) {
   return (m & 3) ? 1 : 4;
 }
 
+// the argument checks that open the bilinear / nearest resize entry points and their gradients (a, b: the two tensors; the dtype test
+// refuses the other build's 16-bit code, or garbage)
+static inline bool resize_args_ok(const void* a, const void* b, int N, int H, int W, int C, int factor, int ldo, int coff, int dtype) {
+  return stp_dtype_ok(dtype) && a && b && N > 0 && H > 0 && W > 0 && C > 0 && factor >= 1 && ldo >= coff + C && coff >= 0;
+}
+
 static inline int pool_vl(int cg) { return cg < 8 ? cg : 8; }   // 8 vector lanes = 128 contiguous bytes per pixel and workgroup
 
 // second stage of a split reduction: dst[i] (+)= scale * sum_s part[s][i], s in ascending order
@@ -232,6 +238,34 @@ static inline int split_rows(int64_t blocks, int rows, int cols) {
   const int want = (int)ceil_div((int64_t)1024, blocks);
   const int rps = (int)ceil_div(rows, want < rows ? want : rows);
   return rps < 1 ? 1 : rps;
+}
+
+// THE statement of the split of a rows x rows tap reduction (an average-pooling window, the (2f)^2 taps of a resize gradient) over a
+// workspace: `items` outputs (windows, input pixels) of C channels in cg vector groups, VL of them per workgroup -> rows per split,
+// splits, and the bytes of the fp32 table part[S][items][C] that the splits write and split_combine_launch sums.
+struct SplitPlan { int rps, S; size_t bytes; };
+static inline SplitPlan split_plan(int64_t items, int C, int cg, int VL, int rows) {
+  SplitPlan p;
+  p.rps = split_rows(items * ceil_div(cg, VL), rows, rows);
+  p.S = ceil_div(rows, p.rps);
+  p.bytes = (size_t)p.S * items * C * sizeof(float);
+  return p;
+}
+// no workspace, or one too small for the table: one pass that writes the destination itself
+static inline SplitPlan split_plan_fit(SplitPlan p, int rows, const void* workspace, size_t workspace_bytes) {
+  if (p.S > 1 && (!workspace || workspace_bytes < p.bytes)) { p.rps = rows; p.S = 1; p.bytes = 0; }
+  return p;
+}
+// what a *_workspace_bytes query that does not know the dtype answers: the larger table of either vector width the launch may pick
+// (channel counts that neither width divides are counted in rounded-up groups); 0 where neither splits
+static inline size_t split_bytes_either_width(int64_t items, int C, int rows) {
+  size_t need = 0;
+  for (int V = 4; V <= 8; V += 4) {
+    const int cg = ceil_div(C, V);
+    const SplitPlan p = split_plan(items, C, cg, pool_vl(cg), rows);
+    if (p.S > 1) need = need > p.bytes ? need : p.bytes;
+  }
+  return need;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -20,6 +20,8 @@ from oracle import losses as olosses  # noqa: E402
 from oracle import np_ops  # noqa: E402
 from oracle import optim as ooptim  # noqa: E402
 
+import _resize_bwd_cases as RB  # noqa: E402
+
 
 @pytest.fixture(scope="module")
 def ops():
@@ -1942,40 +1944,40 @@ def test_batchnorm_apply_fused_with_the_max_pooling_behind_it(ops, case, dtype):
                   None, ops.ptr(b), relu, ops.stream())
 
 
-@pytest.mark.parametrize("case", [(2, 12, 24, 24, 24, 0, 8), (1, 16, 64, 8, 8, 0, 4), (2, 6, 10, 8, 24, 8, 2), (1, 9, 33, 16, 16, 0, 8),
-                                  (2, 5, 7, 16, 48, 16, 1), (1, 8, 8, 128, 320, 64, 1),       # factor 1 = a channel slice copied / added back
-                                  # tiny maps, large factors, a slice of a wide tensor (PSPNet's pyramid levels): the separable two-pass form
-                                  (2, 1, 1, 128, 320, 64, 32), (1, 2, 2, 512, 1024, 512, 16), (2, 3, 3, 64, 192, 128, 24), (1, 6, 6, 256, 256, 0, 8),
-                                  # wide slices of a concatenation (FPN's pyramid levels: round 6, resize_bilinear_bwd_tile_kernel): two channel
-                                  # chunks, ragged column segments, an odd row count (a row pair with one row), factors 2 .. 16 and a factor of 3
-                                  (1, 18, 20, 128, 512, 128, 8), (2, 17, 33, 64, 192, 64, 4), (1, 40, 36, 128, 512, 384, 2), (1, 17, 3, 32, 32, 0, 16),
-                                  (1, 20, 20, 48, 48, 0, 3)])
+@pytest.mark.parametrize("case", RB.SLICE_CASES)
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_bilinear_resize_gradient_of_class_logits_and_of_an_unresized_slice(ops, case, dtype):
     """Round 5: resize_bilinear_bwd_rows_kernel - the gradient of the x4 / x8 bilinear resize of class logits (channel count padded to
     the 16-byte group: PSPNet's 20 classes in rows of 24, FPN's 3 in rows of 8), output rows streamed whole through LDS - and
     slice_copy_kernel (factor 1: the concatenation level that keeps its resolution).  Against torch autograd of the oracle's TF-1.x
-    resize; channel slices (ldo / coff), accumulate, edge rows and columns, replay bit-identical."""
+    resize; channel slices (ldo / coff), accumulate, edge rows and columns, replay bit-identical.  The other forms of the gradient
+    (tests/_resize_bwd_cases.py names the one each case is for: the two-pass form for tiny maps, the row-pair tile kernel, the
+    workgroup-per-pixel kernel split over the workspace) run through the same checks; the form is asserted with the arguments of
+    each launch, and the cases that name a second form run once more without a workspace."""
     from oracle import nets as onets
     from segmentation_training_pipeline_amd import _lib
-    n, h, w, c, ldo, coff, f = case
-    rng = np.random.RandomState(hash(case) % 2**31)
+    shape, forms, bare = case
+    n, h, w, c, ldo, coff, f = shape
+    rng = np.random.RandomState(hash(shape) % 2**31)
     xt = torch.zeros(n, c, h, w, requires_grad=True)
     gy = q(rng.randn(n, h * f, w * f, ldo), dtype)
     onets.resize_bilinear_tf1(xt, f).backward(torch.from_numpy(gy[..., coff:coff + c]).permute(0, 3, 1, 2))
     ref = xt.grad.permute(0, 2, 3, 1).numpy()
     gd = dev(gy, dtype)
     base = q(rng.randn(n, h, w, c), dtype)
-    outs = []
-    for acc in (0, 1, 1):
-        dx = dev(base, dtype) if acc else torch.full((n, h, w, c), float("nan"), dtype=TD[dtype], device=DEV)
-        wsb = int(_lib.load().stp_resize_bilinear_bwd_workspace_bytes(n, h, w, c, f))
-        ws = keep(torch.empty(max(wsb // 4, 1), dtype=torch.float32, device=DEV))
-        _lib.call("stp_resize_bilinear_bwd", ops.ptr(gd), ops.ptr(dx), n, h, w, c, f, ldo, coff, ops.dt(dx), acc, ops.ptr(ws) if wsb else None, wsb, ops.stream())
-        want = ref + (base if acc else 0.0)
-        np.testing.assert_allclose(host(dx), want, atol=tol(want, dtype, 1.0))
-        outs.append(host(dx).copy())
-    assert np.array_equal(outs[1], outs[2])
+    for use_ws, expect in ((True, forms),) + (((False, bare),) if bare is not None else ()):
+        outs = []
+        for acc in (0, 1, 1):
+            dx = dev(base, dtype) if acc else torch.full((n, h, w, c), float("nan"), dtype=TD[dtype], device=DEV)
+            wsb = int(_lib.load().stp_resize_bilinear_bwd_workspace_bytes(n, h, w, c, f)) if use_ws else 0
+            ws = keep(torch.empty(max(wsb // 4, 1), dtype=torch.float32, device=DEV))
+            assert RB.form_of(ops.ptr(gd), ops.ptr(dx), n, h, w, c, f, ldo, coff, dtype, ops.ptr(ws) if wsb else None, wsb) == RB.want(expect, dtype)
+            _lib.call("stp_resize_bilinear_bwd", ops.ptr(gd), ops.ptr(dx), n, h, w, c, f, ldo, coff, ops.dt(dx), acc, ops.ptr(ws) if wsb else None, wsb,
+                      ops.stream())
+            want = ref + (base if acc else 0.0)
+            np.testing.assert_allclose(host(dx), want, atol=tol(want, dtype, 1.0))
+            outs.append(host(dx).copy())
+        assert np.array_equal(outs[1], outs[2])
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
@@ -1986,7 +1988,7 @@ def test_tf1_bilinear_resize_into_channel_slice_and_gradient(ops, dtype, factor)
     from oracle import nets as onets
     from segmentation_training_pipeline_amd import _lib
     rng = np.random.RandomState(41)
-    n, h, w, c, ldo, coff = 2, 5, 7, 8, 24, 8
+    n, h, w, c, ldo, coff = RB.TF1_SHAPE
     x = q(rng.randn(n, h, w, c), dtype)
     xt = torch.from_numpy(x).permute(0, 3, 1, 2).clone().requires_grad_(True)
     ref = onets.resize_bilinear_tf1(xt, factor)
@@ -2000,8 +2002,9 @@ def test_tf1_bilinear_resize_into_channel_slice_and_gradient(ops, dtype, factor)
     assert np.all(got[..., :coff] == 7.0) and np.all(got[..., coff + c:] == 7.0)          # neighbours' slices untouched
     for acc in (0, 1):
         base = q(rng.randn(n, h, w, c), dtype)
-        dx = dev(base, dtype)
-        _lib.call("stp_resize_bilinear_bwd", ops.ptr(dev(gy, dtype)), ops.ptr(dx), n, h, w, c, factor, ldo, coff, ops.dt(dx), acc, None, 0, ops.stream())
+        dx, gd = dev(base, dtype), dev(gy, dtype)
+        assert RB.form_of(ops.ptr(gd), ops.ptr(dx), n, h, w, c, factor, ldo, coff, dtype, None, 0) == RB.want(RB.TF1_FORMS[factor], dtype)
+        _lib.call("stp_resize_bilinear_bwd", ops.ptr(gd), ops.ptr(dx), n, h, w, c, factor, ldo, coff, ops.dt(dx), acc, None, 0, ops.stream())
         want = xt.grad.permute(0, 2, 3, 1).numpy() + (base if acc else 0)
         np.testing.assert_allclose(host(dx), want, atol=tol(want, dtype, 1.0))
     # PSPNet pyramid pooling: AveragePooling2D(k, k) and its gradient
@@ -2359,13 +2362,15 @@ def test_pyramid_pooling_geometry_resize_and_pool(ops, dtype, geom):
     _lib.call("stp_resize_bilinear", ops.ptr(xd), ops.ptr(y), n, h, w, c, f, c, 0, ops.dt(xd), ops.stream())
     np.testing.assert_allclose(host(y), ref.detach().permute(0, 2, 3, 1).numpy(), atol=tol(x, dtype, 0.5))
     wsb = int(_lib.load().stp_resize_bilinear_bwd_workspace_bytes(n, h, w, c, f))
-    assert wsb > 0 or 4 * f * f < 1024                       # the large-factor cases do take the split path
+    assert wsb > 0 or 4 * f * f < 1024                       # the query asks for a workspace for every large-factor case (which form then
+                                                             # runs is asserted below: none of these geometries reaches the split launch)
     ws = torch.empty(max(wsb, 4) // 4, dtype=torch.float32, device=DEV)
     for acc, use_ws in ((0, True), (1, True), (0, False), (1, False)):
         base = q(rng.randn(n, h, w, c) * f, dtype)
-        dx = dev(base, dtype)
-        _lib.call("stp_resize_bilinear_bwd", ops.ptr(dev(gy, dtype)), ops.ptr(dx), n, h, w, c, f, c, 0, ops.dt(dx), acc,
-                  ops.ptr(ws) if use_ws and wsb else None, wsb if use_ws else 0, ops.stream())
+        dx, gd = dev(base, dtype), dev(gy, dtype)
+        wp, wb = (ops.ptr(ws) if use_ws and wsb else None), (wsb if use_ws else 0)
+        assert RB.form_of(ops.ptr(gd), ops.ptr(dx), n, h, w, c, f, c, 0, dtype, wp, wb) == RB.want(RB.GEOM_FORMS[geom][0 if use_ws else 1], dtype)
+        _lib.call("stp_resize_bilinear_bwd", ops.ptr(gd), ops.ptr(dx), n, h, w, c, f, c, 0, ops.dt(dx), acc, wp, wb, ops.stream())
         want = xt.grad.permute(0, 2, 3, 1).numpy() + (base if acc else 0)
         np.testing.assert_allclose(host(dx), want, atol=tol(want, dtype, 1.0))
     # the pooling that produced such a map: window f x f over the (h*f, w*f) feature

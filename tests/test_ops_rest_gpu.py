@@ -1,11 +1,11 @@
 """GPU parity tests of the entry points that only whole-step tests used to reach: the pooling / resize / element-wise kernels of
-pool.hip, resize.hip and elementwise.hip, the spatial dropout and the softmax activation of deeplab.hip, the loss on class probabilities (loss_prob.hip), the
+pool.hip, upsample2x.hip, resize.hip and elementwise.hip, the spatial dropout and the softmax activation of deeplab.hip, the loss on class probabilities (loss_prob.hip), the
 batched class-collapsed weight copy (weight_prep.hip).  Each C-ABI entry point is called directly and compared with a plain float64 numpy (or torch-CPU float64
 autograd) restatement of the same operation, never with a second run of a kernel.
 
 Conventions as in test_ops_gpu.py: inputs are rounded through the storage dtype first (``q``), device temporaries stay alive until the
 test ends, ``dtype`` runs over fp32 / bf16 / fp16 with the fp16 cases routed to libstp_hip_f16.so.  Every group has a case larger than
-the grid cap of its launcher (524 288 threads in pool.hip / resize.hip / elementwise.hip, 4 194 304 in deeplab.hip and loss_prob.hip) so that the grid-stride loop takes a second
+the grid cap of its launcher (524 288 threads in pool.hip / upsample2x.hip / resize.hip / elementwise.hip, 4 194 304 in deeplab.hip and loss_prob.hip) so that the grid-stride loop takes a second
 trip, a case with ragged extents (odd N, H != W, C % 8 == 4), and outputs are pre-filled with NaN so that an element nobody wrote shows.
 Bit-equality needs no tolerance; everywhere else the bound is the one the sibling test of the same family uses (``tol``: one output
 rounding plus fp32 accumulation).  Refusals are checked on the return code; a refused call launches nothing.
