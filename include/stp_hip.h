@@ -1221,6 +1221,51 @@ int stp_sigmoid_bce_dice_weighted(const void* logits, const uint8_t* target, int
                                   float* scalars, void* dlogits, int32_t dl_channels, float grad_scale, void* workspace,
                                   size_t workspace_bytes, const float* pixel_weights, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Boundary scores of two masks on the device (csrc/boundary.hip): the counters of the Hausdorff distance, its percentile form (HD95), the
+ * average symmetric surface distance and the boundary F-score / surface Dice at pixel tolerances.  uint8, int32 and int64 only (both builds
+ * export the same code); no float arithmetic; exact integer work, equal to the host statement (tests/_boundary_reference.py) and
+ * byte-identical from run to run.  Only integer atomics (atomicAdd on counters, histogram bins and the list cursor, atomicMax); no workgroup
+ * waits for another.  The rules of the component entries hold: STP_E_BADARG before any launch for a NULL pointer, a bad size and what is
+ * listed below; never a synchronisation or an allocation; workspace 8-byte aligned and >= stp_surface_distances_workspace_bytes(h, w) (0
+ * for sizes it refuses), else STP_E_WORKSPACE.  Sizes: 1 <= h, w <= 32767, the limits of stp_mask_edt, else BADARG.
+ *
+ *   pred, truth : uint8 masks [h][w]; any non-zero byte is foreground.
+ *   surface     : S(M) = the foreground pixels with at least one 4-neighbour that is background or lies outside the image:
+ *                 M & ~scipy.ndimage.binary_erosion(M, generate_binary_structure(2, 1)) with border_value = 0 - the surface of
+ *                 medpy.metric.binary with its default connectivity.
+ *   distances   : for p in S(pred): D2(p) = min over q in S(truth) of |p - q|^2 (int32), and likewise from S(truth) to S(pred):
+ *                 distance_transform_edt(~S(truth))**2 at the pixels of S(pred), as an exact integer.
+ *   counters    : per direction d (0: pred -> truth, 1: truth -> pred), int64:
+ *                   n        the surface pixel count (of pred for d = 0, of truth for d = 1)
+ *                   max D2   -1 when n == 0 or the other surface is empty
+ *                   sum q    q = floor(sqrt(D2 * 65536)) = floor(256 * distance), an exact integer square root (q * q <= D2 * 65536 <
+ *                            (q + 1)^2; D2 * 65536 < 2^47), found bit by bit in int64: a fixed-point distance of 1/256 pixel
+ *                   within[k] for k < T: the surface pixels with D2 <= c2[k]
+ *                 c2: a HOST pointer to T int32 (may be NULL when T = 0); 0 <= T <= 16, c2[k] >= 0, strictly ascending, else BADARG.  A
+ *                 tolerance tau in pixels is c2 = floor(tau * tau).
+ *   percentile  : over the multiset of BOTH directions' D2, n = n0 + n1 values (medpy's hd95: np.percentile(hstack(...))).  1 <= pct_den <=
+ *                 1000, 0 <= pct_num <= pct_den, else BADARG.  In int64 on the device: pos = pct_num * (n - 1), j = pos / pct_den, rem = pos
+ *                 % pct_den; lo = the j-th smallest D2 (0-based), hi = the min(j + 1, n - 1)-th.  The host forms sqrt(lo) + rem / pct_den *
+ *                 (sqrt(hi) - sqrt(lo)): numpy's linear percentile of the distances.
+ *   empty       : when one surface is empty every distance-derived entry of BOTH directions is its "none" value - max -1, sum 0, within 0,
+ *                 lo = hi = -1, rem = 0; both n are still written.
+ *   out         : int64, device, 8-byte aligned, 2 * (3 + T) + 3 entries, all written: per direction (n, max D2, sum q, within[0..T)),
+ *                 then (lo, hi, rem).
+ *
+ *   stp_surface_distances : 12 launches: clear; the surfaces of both masks (a wave owns 64 pixels of a row, left / right neighbours from
+ *                 its ballot) as the images stp_mask_edt takes; stp_mask_edt twice; reduce (max, sum q, within per wave in registers, per
+ *                 workgroup in LDS, one atomic per counter; the D2 values appended to one list by ballot + prefix popcount; the first digit
+ *                 histogram); an exact radix select of both ranks over the list, digits of 11 + 10 + 10 bits: pick, histogram, pick,
+ *                 histogram, pick.  Histograms are private to a wave in LDS, merged per workgroup and added to a global table; a pick is
+ *                 one workgroup that scans the table in bin order and carries (prefix, rank) for both ranks - two histograms when they
+ *                 fall into different bins.  n, j and the list's length are read on the device: the list launches cover 2 h w values and
+ *                 return past the cursor.  The list's order is unspecified and nothing depends on it.  Workspace: about 20 bytes per
+ *                 pixel. */
+size_t stp_surface_distances_workspace_bytes(int32_t h, int32_t w);
+int stp_surface_distances(const uint8_t* pred, const uint8_t* truth, int32_t h, int32_t w, const int32_t* c2, int32_t T, int32_t pct_num,
+                          int32_t pct_den, int64_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

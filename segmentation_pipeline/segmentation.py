@@ -965,6 +965,21 @@ class PipelineConfig(generic.GenericTaskConfig):
         return {"score": float(images.mean()), "by_iou": {t: float(v) for t, v in zip(ts, per.mean(axis=0))},
                 "images": [(i, float(v)) for i, v in zip(ids, images)], "counts": counts}
 
+    def _sweep_thresholds(self, thresholds):
+        """The thresholds of a sweep over masks: d / 20 for d = 1..19 by default, else 1 to 64 finite values, strictly ascending as
+        float32; a softmax head takes none and sweeps the one cell 0.5."""
+        if self._softmax_head():
+            if thresholds is not None:
+                raise ValueError("a softmax head has one label per pixel: the mask of `channel` is argmax == channel and takes no thresholds")
+            return [0.5]
+        thresholds = [d / 20 for d in range(1, 20)] if thresholds is None else [float(t) for t in thresholds]
+        t32 = np.asarray(thresholds, np.float32)
+        if not 1 <= len(thresholds) <= 64:
+            raise ValueError("1 to 64 thresholds in one sweep: got %d" % len(thresholds))
+        if not np.isfinite(t32).all() or not (np.diff(t32) > 0).all():
+            raise ValueError("thresholds must be finite and strictly ascending (as float32)")
+        return thresholds
+
     def find_object_threshold(self, ds, fold, stage=-1, negatives="real", ttflips=None, thresholds=None, min_sizes=(0,), opening=0, closing=0,
                               channel=0, area_threshold=0, metric="f2", iou_thresholds=None, truth="mask"):
         """``find_threshold`` for the score the masks are judged on: the cell of the grid ``thresholds`` x ``min_sizes`` - the two
@@ -973,17 +988,7 @@ class PipelineConfig(generic.GenericTaskConfig):
         stp_label_match.  All counters ([images, cells, T + 3] int64) stay on the device and come back in one copy.  A softmax head
         takes ``channel`` and no ``thresholds``: only ``min_sizes`` are swept.  Returns ``((best_threshold, best_min_size), {(threshold,
         min_size): score})``; the first cell in thresholds-major order wins a tie."""
-        if self._softmax_head():
-            if thresholds is not None:
-                raise ValueError("a softmax head has one label per pixel: the mask of `channel` is argmax == channel and takes no thresholds")
-            thresholds = [0.5]
-        else:
-            thresholds = [d / 20 for d in range(1, 20)] if thresholds is None else [float(t) for t in thresholds]
-            t32 = np.asarray(thresholds, np.float32)
-            if not 1 <= len(thresholds) <= 64:
-                raise ValueError("1 to 64 thresholds in one sweep: got %d" % len(thresholds))
-            if not np.isfinite(t32).all() or not (np.diff(t32) > 0).all():
-                raise ValueError("thresholds must be finite and strictly ascending (as float32)")
+        thresholds = self._sweep_thresholds(thresholds)
         min_sizes = list(min_sizes)
         if not 1 <= len(min_sizes) <= 64:
             raise ValueError("1 to 64 min_sizes in one sweep: got %d" % len(min_sizes))
@@ -1025,6 +1030,173 @@ class PipelineConfig(generic.GenericTaskConfig):
         pairs = pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))]          # the device's order is unspecified: sorted by (a, b)
         areas = areas.cpu().numpy()
         return pairs, areas[0], areas[1]
+
+    # ---------------------------------------------------------------- boundary scores on the device (csrc/boundary.hip)
+    BOUNDARY_METRICS = ("boundary_f", "surface_dice", "hd", "hd_percentile", "assd")      # the first two: larger is better
+    BOUNDARY_SCORES = ("boundary_precision", "boundary_recall", "boundary_f", "surface_dice")
+    PCT_DEN = 1000                    # percentiles are exact fractions n / 1000 of 1: one decimal place of a per cent
+    MAX_TOLERANCE = 46340             # floor(tau * tau) stays an int32
+
+    @classmethod
+    def _boundary_args(cls, tolerances, percentile):
+        """-> (the tolerances as given, their squared forms c2 = floor(tau * tau), the percentile's numerator over 1000): 0 to 16
+        tolerances, real finite numbers in 0..46340 whose c2 ascend strictly; a percentile in 0..100 with at most one decimal place."""
+        taus = list(tolerances)
+        if len(taus) > 16:
+            raise ValueError("0 to 16 tolerances: got %d" % len(taus))
+        c2 = []
+        for tau in taus:
+            if (isinstance(tau, (bool, np.bool_)) or not isinstance(tau, (int, float, np.integer, np.floating)) or not np.isfinite(tau)
+                    or not 0 <= tau <= cls.MAX_TOLERANCE):
+                raise ValueError("tolerances are distances in pixels, finite numbers in 0..%d: got %r" % (cls.MAX_TOLERANCE, tau))
+            c2.append(int(np.floor(float(tau) * float(tau))))
+        if any(b <= a for a, b in zip(c2, c2[1:])):
+            raise ValueError("tolerances must ascend strictly, as floor(tau * tau): got %r" % (taus,))
+        p = float(percentile) if isinstance(percentile, (int, float, np.integer, np.floating)) and not isinstance(percentile, bool) else -1.0
+        num = int(round(p * 10)) if np.isfinite(p) else -1
+        if not 0 <= num <= cls.PCT_DEN or abs(p * 10 - num) > 1e-6:
+            raise ValueError("percentile is a number in 0..100 with at most one decimal place: got %r" % (percentile,))
+        return taus, c2, num
+
+    @classmethod
+    def boundary_scores(cls, counts, tolerances):
+        """The boundary scores of one image from stp_surface_distances' counters (int64 [2 * (3 + T) + 3]: per direction n, max D2, sum of
+        floor(256 d), within per tolerance; then lo, hi, rem of the percentile) -> ``{"hd", "hd_percentile", "assd": float,
+        "boundary_precision", "boundary_recall", "boundary_f", "surface_dice": {tolerance: float}, "counts"}``.  Both surfaces empty:
+        distances 0 and scores 1; exactly one empty: distances inf and scores 0."""
+        counts = np.asarray(counts, np.int64)
+        T = len(tolerances)
+        a, b = [int(v) for v in counts[:3 + T]], [int(v) for v in counts[3 + T:2 * (3 + T)]]
+        lo, hi, rem = (int(v) for v in counts[2 * (3 + T):])
+        res = {"counts": counts}
+        if a[0] == 0 or b[0] == 0:
+            both = a[0] == 0 and b[0] == 0
+            res["hd"] = res["hd_percentile"] = res["assd"] = 0.0 if both else float("inf")
+            for name in cls.BOUNDARY_SCORES:
+                res[name] = {tau: 1.0 if both else 0.0 for tau in tolerances}
+            return res
+        res["hd"] = float(np.sqrt(float(max(a[1], b[1]))))
+        res["hd_percentile"] = float(np.sqrt(float(lo)) + rem / cls.PCT_DEN * (np.sqrt(float(hi)) - np.sqrt(float(lo))))
+        res["assd"] = (a[2] + b[2]) / (256 * (a[0] + b[0]))
+        for name in cls.BOUNDARY_SCORES:
+            res[name] = {}
+        for k, tau in enumerate(tolerances):
+            p, r = a[3 + k] / a[0], b[3 + k] / b[0]
+            res["boundary_precision"][tau], res["boundary_recall"][tau] = p, r
+            res["boundary_f"][tau] = 2 * p * r / (p + r) if p + r > 0 else 0.0
+            res["surface_dice"][tau] = (a[3 + k] + b[3 + k]) / (a[0] + b[0])
+        return res
+
+    @staticmethod
+    def surface_distances(pred_mask, truth_mask, tolerances=(1, 2, 3), percentile=95):
+        """The boundary scores of two numpy masks [h, w] (any non-zero value is foreground), on the device (stp_surface_distances).  The
+        surface of a mask is its foreground pixels with a 4-neighbour that is background or outside the image (medpy.metric.binary's,
+        default connectivity); every surface pixel has its exact Euclidean distance to the other mask's surface.  ``hd``: the Hausdorff
+        distance, the largest of them; ``hd_percentile``: numpy's linear ``percentile`` of both directions' distances together (95:
+        medpy's hd95); ``assd``: their mean, each distance floored to 1/256 pixel; per tolerance tau (compared as D2 <= floor(tau *
+        tau)) ``boundary_precision`` = the pred surface within tau of the truth surface, ``boundary_recall`` the converse,
+        ``boundary_f`` their harmonic mean and ``surface_dice`` the pooled fraction.  See ``boundary_scores`` for the dict."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        taus, c2, num = PipelineConfig._boundary_args(tolerances, percentile)
+        p, g = np.asarray(pred_mask), np.asarray(truth_mask)
+        if p.ndim != 2 or p.shape != g.shape or p.size == 0 or p.dtype.kind not in "iubf" or g.dtype.kind not in "iubf":
+            raise ValueError("surface_distances takes two non-empty numeric masks of one shape [h, w]")
+        h, w = (int(v) for v in p.shape)
+        if max(h, w) > 32767:
+            raise ValueError("surface_distances takes images of at most 32767 x 32767 pixels")
+        pd, gd = (torch.from_numpy(np.ascontiguousarray(a != 0).view(np.uint8)).to("cuda") for a in (p, g))
+        out = torch.empty(2 * (3 + len(c2)) + 3, dtype=torch.int64, device="cuda")
+        ws = torch.empty(ops.surface_distances_workspace_bytes(h, w), dtype=torch.uint8, device="cuda")
+        ops.surface_distances(pd, gd, h, w, c2, num, PipelineConfig.PCT_DEN, out, ws)
+        return PipelineConfig.boundary_scores(out.cpu().numpy(), taus)
+
+    def _boundary_counts(self, ds, fold, stage, negatives, ttflips, thresholds, mode, opening, closing, channel, min_size, area_threshold, c2,
+                         pct_num):
+        """-> (ids, int64 [images, thresholds, 2 * (3 + T) + 3]): per validation item of ``fold`` the network runs once; per threshold
+        the mask of ``predict_masks_ex`` and stp_surface_distances against the item's mask plane.  The counters stay on the device until
+        the one copy at the end."""
+        from segmentation_training_pipeline_amd import ops
+        import torch
+        self._check_tta(ttflips)
+        folds = self.kfold(ds, range(0, len(ds)))
+        indexes = [int(i) for i in folds.sampledIndexes(fold, False, negatives)]
+        if not indexes:
+            raise ValueError("fold %r has no validation items" % (fold,))
+        m = self.load_model(fold, stage)
+        dev, B = m.impl.device, m.impl.batch
+        counts = torch.empty((len(indexes), len(thresholds), 2 * (3 + len(c2)) + 3), dtype=torch.int64, device=dev)
+        ids = []
+        for s in range(0, len(indexes), B):
+            items = [ds[i] for i in indexes[s:s + B]]
+            for j, (it, probs) in enumerate(zip(items, self._predict_maps_device([m], ttflips, items)[0])):
+                h, w = int(probs.shape[0]), int(probs.shape[1])
+                ids.append(it.id)
+                y = np.asarray(it.y)
+                plane = y if y.ndim == 2 else y[:, :, channel if y.shape[2] > 1 else 0]
+                if plane.shape != (h, w):
+                    raise ValueError("item %r: a %s mask for a %d x %d image" % (it.id, plane.shape, h, w))
+                target = torch.from_numpy(np.ascontiguousarray(plane != 0).view(np.uint8)).to(dev)
+                ws = torch.empty(ops.surface_distances_workspace_bytes(h, w), dtype=torch.uint8, device=dev)
+                for c, threshold in enumerate(thresholds):
+                    mask = self._device_mask(probs, mode, float(threshold), int(opening), int(closing), int(channel), int(min_size),
+                                             int(area_threshold))
+                    ops.surface_distances(mask, target, h, w, c2, pct_num, self.PCT_DEN, counts[s + j, c], ws)
+        return ids, counts.cpu().numpy()          # the only copy back
+
+    @classmethod
+    def _boundary_means(cls, rows, taus, keep):
+        """The means of the per-image dicts ``rows`` over the images ``keep`` (nan without any)."""
+        rows = [r for r, k in zip(rows, keep) if k]
+        mean = lambda vs: float(np.mean(vs)) if vs else float("nan")      # noqa: E731
+        res = {name: mean([r[name] for r in rows]) for name in ("hd", "hd_percentile", "assd")}
+        for name in cls.BOUNDARY_SCORES:
+            res[name] = {tau: mean([r[name][tau] for r in rows]) for tau in taus}
+        return res
+
+    def score_boundaries(self, ds, fold, stage=-1, negatives="real", ttflips=None, threshold=0.5, opening=0, closing=0, channel=0, min_size=0,
+                         area_threshold=0, tolerances=(1, 2, 3), percentile=95):
+        """Where the contour lies: ``surface_distances`` of ``predict_masks_ex``'s masks against the items' masks on the validation items
+        of ``fold`` (chosen as ``find_threshold`` chooses them).  Per image, all on the device: the finished map at the image's own size,
+        the mask (threshold, opening, closing, ``min_size``, ``area_threshold``), stp_surface_distances; only the counters come back, in
+        one copy.  Returns the means of ``boundary_scores``' entries over the images whose distances are finite - an image with exactly
+        one empty surface has none -, ``"undefined"``: the number of images left out of those means, ``"images"``: [(id,
+        ``boundary_scores``' dict)] and ``"counts"``: int64 [images, 2 * (3 + T) + 3]."""
+        mode = self._mask_mode(threshold, opening, closing, channel, min_size, area_threshold)
+        taus, c2, num = self._boundary_args(tolerances, percentile)
+        ids, counts = self._boundary_counts(ds, fold, stage, negatives, ttflips, [threshold], mode, opening, closing, channel, min_size,
+                                            area_threshold, c2, num)
+        counts = counts[:, 0]
+        rows = [self.boundary_scores(c, taus) for c in counts]
+        keep = [np.isfinite(r["hd"]) for r in rows]
+        res = self._boundary_means(rows, taus, keep)
+        res.update({"undefined": len(rows) - int(sum(keep)), "images": list(zip(ids, rows)), "counts": counts})
+        return res
+
+    def find_boundary_threshold(self, ds, fold, stage=-1, negatives="real", ttflips=None, thresholds=None, opening=0, closing=0, channel=0,
+                                min_size=0, area_threshold=0, metric="boundary_f", tolerance=2, percentile=95):
+        """``find_threshold`` for the contour: the threshold (default d / 20 for d = 1..19) whose ``score_boundaries`` entry ``metric`` is
+        best - the largest ``"boundary_f"`` / ``"surface_dice"`` at ``tolerance``, the smallest ``"hd"`` / ``"hd_percentile"`` /
+        ``"assd"``.  Per image the network runs once; per threshold: the mask and stp_surface_distances; all counters come back in one
+        copy.  An image whose distances are undefined at any threshold is left out of every threshold's mean.  A softmax head takes
+        ``channel`` and no ``thresholds``.  Returns ``(best_threshold, {threshold: score})``; the first threshold wins a tie."""
+        if metric not in self.BOUNDARY_METRICS:
+            raise ValueError("metric %r: one of %s" % (metric, ", ".join(self.BOUNDARY_METRICS)))
+        thresholds = self._sweep_thresholds(thresholds)
+        mode = 0
+        for t in thresholds:
+            mode = self._mask_mode(t, opening, closing, channel, min_size, area_threshold)
+        taus, c2, num = self._boundary_args((tolerance,), percentile)
+        _, counts = self._boundary_counts(ds, fold, stage, negatives, ttflips, thresholds, mode, opening, closing, channel, min_size,
+                                          area_threshold, c2, num)
+        rows = [[self.boundary_scores(c, taus) for c in image] for image in counts]
+        keep = [all(np.isfinite(r["hd"]) for r in image) for image in rows]
+        scores = []
+        for c in range(len(thresholds)):
+            means = self._boundary_means([image[c] for image in rows], taus, keep)
+            scores.append(means[metric][taus[0]] if metric in self.BOUNDARY_SCORES else means[metric])
+        best = int(np.argmax(scores)) if metric in self.BOUNDARY_SCORES else int(np.argmin(scores))
+        return thresholds[best], dict(zip(thresholds, scores))
 
     # ---------------------------------------------------------------- touching objects split on the device (csrc/split.hip)
     MAX_SPLIT = 1024

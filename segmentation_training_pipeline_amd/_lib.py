@@ -254,6 +254,8 @@ SIGNATURES = {
     "stp_border_weight": (i32, [vp, i32, i32, i32, f32, f32, i32, f32, f32, vp, vp, vp, vp, sz, vp]),
     # stp_sigmoid_bce_dice's list with the pixel weights in front of the stream
     "stp_sigmoid_bce_dice_weighted": (i32, [vp, vp, i64, i32, f32, f32, vp, vp, i32, f32, vp, sz, vp, vp]),
+    "stp_surface_distances_workspace_bytes": (sz, [i32, i32]),
+    "stp_surface_distances": (i32, [vp, vp, i32, i32, C.POINTER(i32), i32, i32, i32, vp, vp, sz, vp]),
 }
 
 _libs = {}          # storage format ("bf16" | "fp16") -> loaded library

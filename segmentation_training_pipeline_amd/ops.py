@@ -673,6 +673,26 @@ def label_select(labels, h, w, label_cap, sums, boxes, min_area, conf_num, conf_
               _nbytes(workspace), stream())
 
 
+# boundary scores on the device (csrc/boundary.hip): two uint8 masks [h, w] -> the counters of Hausdorff, HD95, ASSD and boundary F
+def surface_distances_workspace_bytes(h, w):
+    return int(_lib.load().stp_surface_distances_workspace_bytes(h, w))
+
+
+def surface_distances(pred, truth, h, w, c2, pct_num, pct_den, out, workspace):
+    """``out`` int64 [2 * (3 + T) + 3] = per direction (pred -> truth, truth -> pred) the surface pixel count, the largest squared distance
+    to the other mask's surface (-1: none), the sum of floor(256 * distance) and the surface pixels within the T squared tolerances ``c2`` (a
+    host sequence of ascending integers), then (lo, hi, rem) of the percentile ``pct_num / pct_den`` over both directions' squared
+    distances (include/stp_hip.h), of the uint8 masks ``pred`` and ``truth`` [h, w]."""
+    if pred.numel() < h * w or truth.numel() < h * w or pred.dtype != torch.uint8 or truth.dtype != torch.uint8:
+        raise ValueError("surface_distances: two uint8 masks of h x w")
+    T = len(c2)
+    if out.dtype != torch.int64 or out.numel() < 2 * (3 + T) + 3:
+        raise ValueError("surface_distances: int64 out [2 * (3 + T) + 3]")
+    arr = (C.c_int32 * max(T, 1))(*[int(v) for v in c2])
+    _lib.call("stp_surface_distances", ptr(_dev(pred)), ptr(_dev(truth)), h, w, arr, T, int(pct_num), int(pct_den), ptr(_dev(out)),
+              ptr(_dev(workspace)), _nbytes(workspace), stream())
+
+
 # U-Net border weight maps on the device (csrc/border_weight.hip): int32 label images [N, H, W] -> the fp32 weight map, and the one-class
 # loss that takes it (csrc/loss_sigmoid.hip)
 def border_weight_workspace_bytes(N, H, W):
