@@ -14,7 +14,7 @@ with ``diff``.  Plans build on ``device="cpu"``: nothing here needs a GPU.
 * An integer of 2^40 or more that resolves to no buffer is an error, not a token.
 
 ``python tests/_plan_dump.py OUT_DIR [plan ...]`` writes ``<plan>@<switch>.txt`` for every cell of PLANS x SWITCHES (or of the named plans)
-and prints one ``cell  records  sha256[:16]`` line each (22 plans x 19 switches = 418 cells; DESIGN.md 4.1 and 4.3 compare such tables).  To compare two versions of
+and prints one ``cell  records  sha256[:16]`` line each (29 plans x 19 switches = 551 cells; DESIGN.md 4.1, 4.3 and 4.9 compare such tables).  To compare two versions of
 the plan builder, run it in a checkout of each and ``diff -r`` the two directories."""
 import bisect
 import ctypes as C
@@ -171,7 +171,8 @@ class _HostLovaszSize(object):
         return 64 * int(count) + 4096 * int(images)
 
 
-def _plan(net, backbone, size, batch, dtype, training=True, frozen=False, in_ch=3, dynamic_loss_scale=False, **kw):
+def _plan(net, backbone, size, batch, dtype, training=True, frozen=False, in_ch=3, dynamic_loss_scale=False, env=None, **kw):
+    """``env``: switches the NETWORK definition reads (nets.py), set around the cell's ``define`` and restored behind it."""
     def build():
         from segmentation_training_pipeline_amd import graph, nets
         plan = graph.Plan(batch, dtype, "cpu", training=training)
@@ -189,7 +190,16 @@ def _plan(net, backbone, size, batch, dtype, training=True, frozen=False, in_ch=
             logits = nets.NETWORKS[net](p, backbone, size, size, in_ch, with_loss=training, **kw)
             if not training and net != "DeepLabV3":
                 (p.sigmoid_out if classes == 1 or kw.get("multilabel") else p.softmax_out)(logits)
-        return plan.define(fn)
+        saved = {k: os.environ.get(k) for k in env or ()}
+        os.environ.update(env or {})
+        try:
+            return plan.define(fn)
+        finally:
+            for k, v in saved.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
     return build
 
 
@@ -219,6 +229,16 @@ PLANS = {
     "unet_r18_64_lovasz_bf16": _plan("Unet", "resnet18", 64, 2, "bf16", loss=(1.0, 1.0, 0.0, 0.0, 0.0, 0.5)),
     "unet_r18_64_softmax3_ex_bf16": _plan("Unet", "resnet18", 64, 2, "bf16", classes=3, loss=(1.0, 0.5, 0.25, 0.125, 0.0625)),
     "unet_r18_64_sigmoid_ex_fp16_dls": _plan("Unet", "resnet18", 64, 2, "fp16", loss=(1.0, 0.5, 0.25, 0.125, 0.0625), dynamic_loss_scale=True),
+    # the layer branches no cell above reaches: maxpool_k, spatial dropout, the nearest resizes, PSPNet's concatenated head, the avgpool
+    # fallback of an fp32 pyramid, and the inference plans of the other networks
+    "fpn_r18_128_nearest_dropout_bf16": _plan("FPN", "resnet18", 128, 2, "bf16", classes=3, dropout=0.25, interpolation="nearest"),
+    "pspnet_r18_192_max_nearest_dropout_bf16": _plan("PSPNet", "resnet18", 192, 2, "bf16", classes=3, psp_pooling_type="max",
+                                                     final_interpolation="nearest", dropout=0.1),
+    "pspnet_r18_192_concat_bf16": _plan("PSPNet", "resnet18", 192, 2, "bf16", classes=3, env={"STP_PSP_SPLIT": "0"}),
+    "pspnet_r18_192_fp32": _plan("PSPNet", "resnet18", 192, 2, "fp32", classes=3),
+    "fpn_r18_128_inference_bf16": _plan("FPN", "resnet18", 128, 2, "bf16", classes=3, training=False),
+    "pspnet_r18_192_inference_bf16": _plan("PSPNet", "resnet18", 192, 2, "bf16", classes=3, training=False),
+    "deeplab_mobilenetv2_96_inference_bf16": _plan("DeepLabV3", "mobilenetv2", 96, 2, "bf16", classes=3, training=False),
 }
 
 SWITCHES = [None, ("STP_HALO", "0"), ("STP_S2D", "0"), ("STP_SCATTER_1X1S2", "0"), ("STP_UPCOLLAPSE", "0"), ("STP_UPCOLLAPSE_BWD", "1"),

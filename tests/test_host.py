@@ -781,6 +781,36 @@ def test_plan_dump_is_stable_and_sees_a_plan_change(monkeypatch):
     assert c != a and "s2d=True" not in c
 
 
+def test_plan_dump_cells_reach_the_layer_branches_they_exist_for(monkeypatch):
+    """The cells of tests/_plan_dump.py that exist for a layer branch define without raising, in their default form, and
+    their launch lists hold the entry points of that branch: maxpool_k, spatial dropout, the nearest resizes, the bilinear resize
+    gradient of concat_resize (PSPNet's concatenated head), the avgpool fallback of the pyramid; an inference plan has no backward."""
+    import _plan_dump
+    for k, _ in _plan_dump.SWITCHES[1:]:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.delenv("STP_PSP_SPLIT", raising=False)
+
+    def names(cell):
+        plan = _plan_dump.PLANS[cell]()
+        assert "STP_PSP_SPLIT" not in os.environ          # (a cell that sets a switch of nets.py restores it)
+        return plan, [r[2] for r in plan.fwd], [r[2] for r in plan.bwd]
+
+    _, fwd, bwd = names("fpn_r18_128_nearest_dropout_bf16")
+    assert "stp_dropout_spatial" in fwd and "stp_dropout_spatial" in bwd and "stp_resize_nearest" in fwd
+    assert bwd.count("stp_resize_nearest_bwd") == 5 and "stp_resize_bilinear_bwd" not in bwd      # concat_resize's four parts + the logits
+    _, fwd, bwd = names("pspnet_r18_192_max_nearest_dropout_bf16")
+    assert fwd.count("stp_maxpool_k") == 4 and bwd.count("stp_maxpool_k_bwd") == 4 and "stp_avgpool" not in fwd
+    assert "stp_dropout_spatial" in fwd and "stp_dropout_spatial" in bwd and bwd.count("stp_resize_nearest_bwd") == 1
+    plan, fwd, bwd = names("pspnet_r18_192_concat_bf16")
+    assert "psp_concat" in plan.tensors and "stp_upsample_sum" not in fwd
+    assert bwd.count("stp_resize_bilinear_bwd") == 5      # concat_resize: the feature map (factor 1) and the four pyramid levels
+    _, fwd, bwd = names("pspnet_r18_192_fp32")
+    assert fwd.count("stp_avgpool") == 4 and bwd.count("stp_avgpool_bwd") == 4 and "stp_avgpool_pyramid" not in fwd
+    for cell in ("fpn_r18_128_inference_bf16", "pspnet_r18_192_inference_bf16", "deeplab_mobilenetv2_96_inference_bf16"):
+        plan, fwd, bwd = names(cell)
+        assert fwd and not bwd and not plan._tape and not any(n.endswith("_bwd") or "wgrad" in n for n in fwd), cell
+
+
 def test_bench_names_every_launch_of_the_headline_plan():
     """bench.py's instrumented pass maps every launch of the step to the kernel the library runs for it (kernel_key): a launch kind
     it does not know (a new tile id) must fail here, on CPU, not in the driver's bench run."""
